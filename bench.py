@@ -90,7 +90,30 @@ def parse():
                          "(default: on when launched with more than one rank)")
     ap.add_argument("--config5-rows", type=int, default=10_000_000)
     ap.add_argument("--config5-groups", type=int, default=1000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the loss) and left in the param store to "
+                         "DIR/<name>.npy, so that two builds can be compared output for output")
     return ap.parse_args()
+
+
+SETTLE_STEPS = 256     # untimed steps between the capture and the timed region (see main)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, store):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the loss SVI.step returned
+    and the parameters it left in the param store (constrained, as pyro.param returns them) -- one .npy each."""
+    import numpy as np
+    arrays = {"loss": np.array([loss], dtype=np.float64)}
+    for name, value in store.items():
+        a = value.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs (at most %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name.replace(os.sep, "_") + ".npy"), a)
 
 
 ROUND = 6       # profiles/r05_*: counter files of another round measured other kernels and are refused
@@ -746,28 +769,33 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
 
-    # The timed region is EXACTLY args.steps steps between barrier + synchronize on both sides.  At the
-    # driver's --steps 20 that is ~1.7 ms of timing, so the block is repeated (a count fixed by the
-    # arguments alone: every rank runs the same number of barriers) and the MEDIAN block is the
-    # headline; every block's time is in the line (`blocks_ms_per_step`).
-    # (The first ~250 replays after a capture run 8-10 % slower than the rest -- DESIGN.md section 3, "the
-    #  step gate"; tools/short_block_ramp.py -- so the blocks cover ~8000 steps: the median then sits in the
-    #  state a real SVI run, thousands of steps long, spends its time in.)
-    nblocks = max(1, min(100, -(-8000 // max(args.steps, 1))))
-    block_s = []
-    for _ in range(nblocks):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            if not graphed:
-                timer.arm()
-            svi.step(X, y)             # returns the loss as a float: one host read per step
-            if graphed_events:
-                kern_ms_list.append(timer.read_last())
+    # The timed region is EXACTLY args.steps steps between barrier + synchronize on both sides, and
+    # ms_per_step is its time over args.steps.  The first ~250 replays after a capture run 8-10 % slower
+    # than the rest ("the step gate"; tools/short_block_ramp.py), so SETTLE_STEPS
+    # untimed steps come first: the timed steps then run in the state a real SVI run, thousands of steps
+    # long, spends its time in.
+    if graphed:
+        for _ in range(SETTLE_STEPS):
+            svi.step(X, y)
         if prearm:
-            svi.pause()                # (inside the timed region: part of what a block of steps costs)
-        sync()
-        block_s.append(time.perf_counter() - t0)
+            svi.pause()
+    # (repetitions of the side measurements below)
+    nblocks = max(1, min(100, -(-8000 // max(args.steps, 1))))
+    loss = None
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        if not graphed:
+            timer.arm()
+        loss = svi.step(X, y)          # returns the loss as a float: one host read per step
+        if graphed_events:
+            kern_ms_list.append(timer.read_last())
+    if prearm:
+        svi.pause()                    # (inside the timed region: part of what the steps cost)
+    sync()
+    block_s = [time.perf_counter() - t0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, pyro.get_param_store())
     # which kernel the headline ran (the secondary measurements below switch image formats)
     headline_planes = bool(on_gpu and kernels.glm_planes_of(X) is not None)
     headline_f16 = headline_planes and kernels.glm_planes_format() == kernels.GLM_PLANES_F16X2
@@ -856,14 +884,14 @@ def main():
     rccl_ranks = 1
     if world > 1:
         t = torch.tensor(block_s, device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)          # max over ranks, block by block
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)          # max over ranks
         block_s = [float(v) for v in t.cpu()]
         # how many ranks the communicator actually holds: a sum of ones through the same backend the
         # gradient all-reduce uses (not the WORLD_SIZE environment variable)
         ones = torch.ones((1,), device=dev, dtype=torch.float32)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         rccl_ranks = int(round(float(ones.item())))
-    elapsed = sorted(block_s)[len(block_s) // 2]           # the median block
+    elapsed = block_s[0]
 
     sharded5 = None
     if args.config5_sharded is None:
@@ -1038,9 +1066,9 @@ def main():
             "unit": "ELBO-grad steps/s (64 particles x 1e6-row plate per step)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "timing": {"blocks": len(block_s), "steps_per_block": args.steps, "statistic": "median block "
-                       "(each block = exactly `steps` steps between barrier + synchronize, max over ranks)",
-                       "blocks_ms_per_step": [round(b / args.steps * 1e3, 5) for b in block_s]},
+            "timing": {"steps": args.steps, "settle_steps": SETTLE_STEPS if graphed else 0,
+                       "statistic": "exactly `steps` steps between barrier + synchronize, max over ranks, after "
+                                    "`settle_steps` untimed steps of the captured step"},
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: Bayesian logistic regression, plate=%d, D=%d, Trace_ELBO "
                                    "num_particles=%d per GPU (vectorised), AutoNormal, Adam; full SVI.step of "

@@ -1136,9 +1136,11 @@ size_t pa_glm_bernoulli_planes_workspace(int64_t N, int64_t D, int64_t P) {
   }
   // (the same for both image formats: the record count is capped at four workgroups per CU)
   const pa::GlmPlanesPlan pl = pa::glm_planes_plan(N, P);
-  // records of the deepest / widest tuning so that the knob never invalidates a workspace
+  // records of the deepest / widest tuning so that the knob never invalidates a workspace: up to four
+  // workgroups per CU, and up to one per 32-row tile (the 1 x 8 wide geometry of glmh_plan)
   const size_t cap = (size_t)pa::cu_count() * 4;
-  const size_t nb = (size_t)pl.nst < cap ? (size_t)(pl.nst < 1 ? 1 : pl.nst) : cap;
+  const size_t ntiles = (size_t)((N + 31) / 32);
+  const size_t nb = ntiles < cap ? (ntiles < 1 ? 1 : ntiles) : cap;
   const size_t rec = 2 * 1024 + 2 * 2 * 32;
   // the partial records, then the fp64 level-1 partials of the in-kernel finalize
   return nb * pl.npass * rec * sizeof(float) +
@@ -1228,6 +1230,7 @@ int pa_glm_bernoulli_planes_fwd_bwd(int format, const void* planes, const float*
     fin.counters = pa::glmf_counters(!capturing);
   }
   const size_t rec_bytes = (size_t)pl.nblocks * pl.npass * (2 * 1024 + 2 * 2 * 32) * sizeof(float);
+  PA_REQUIRE(rec_bytes <= workspace_bytes, "glm_planes: %d x %d records exceed the workspace", pl.nblocks, pl.npass);
   fin.part64 = (double*)((char*)workspace + ((rec_bytes + 15) & ~(size_t)15));
   fin.ll = ll; fin.gw = gw; fin.gb = gb;
   fin.scale = scale; fin.ll_offset = ll_offset;

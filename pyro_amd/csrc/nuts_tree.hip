@@ -666,13 +666,18 @@ __global__ __launch_bounds__(64 * NW) void nuts_tree_advance_kernel(
       const T pe_c = moved ? b_pe : pe_io[chain];
       T eps_next = eps;
       if (flags & RF_ADAPT_STEP) {  // DualAveraging.step (pyro/ops/dual_averaging.py:55-78), H = target - ap
+        // the host's recurrence (pyro_amd/ops/dual_averaging.py) operation for operation -- its float64 weights,
+        // no fused multiply-adds -- so that chains adapted here follow the lock-step chains adapted on the host:
+        // warm-up feeds every rounding difference back through the step size and amplifies it
+#pragma clang fp contract(off)
         T x_avg = run.da[chain * 5], g_avg = run.da[chain * 5 + 1], da_t = run.da[chain * 5 + 2];
         const T prox = run.da[chain * 5 + 3];
         const T g = (T)run.target_accept - ap;
         da_t += T(1);
-        g_avg = (T(1) - T(1) / (da_t + (T)run.da_t0)) * g_avg + g / (da_t + (T)run.da_t0);
-        const T x_t = prox - Num<T>::sqrt_(da_t) / (T)run.da_gamma * g_avg;
-        const T weight = Num<T>::exp_(-(T)run.da_kappa * Num<T>::log_(da_t));
+        const T w_g = (T)(1.0 / ((double)da_t + run.da_t0));
+        g_avg = (T(1) - w_g) * g_avg + w_g * g;
+        const T x_t = prox - g_avg * (T)(sqrt((double)da_t) / run.da_gamma);
+        const T weight = (T)pow((double)da_t, -run.da_kappa);
         x_avg = (T(1) - weight) * x_avg + weight * x_t;
         eps_next = Num<T>::exp_(x_t);
         if constexpr (NW > 1) __syncthreads();    // every thread has read the record
@@ -689,10 +694,13 @@ __global__ __launch_bounds__(64 * NW) void nuts_tree_advance_kernel(
         for (int m = 0; m < NPL; ++m) {
           const int d = c.tid + m * c.NT;
           if (c.ok(m)) {
+#pragma clang fp contract(off)
+            // (pyro_amd/ops/welford.py's update as written: no fused multiply-add)
             T mean = wrow[d], m2 = wrow[D + d];
-            const T pre = zc.x[m] - mean;
-            mean = mean + pre / n;
-            m2 = m2 + pre * (zc.x[m] - mean);
+            const T before = zc.x[m] - mean;
+            mean = mean + before / n;
+            const T after = zc.x[m] - mean;
+            m2 = m2 + before * after;
             wrow[d] = mean;
             wrow[D + d] = m2;
           }
