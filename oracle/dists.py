@@ -58,36 +58,46 @@ def half_normal_log_prob(v, scale):
 
 
 def _xlogy(x, y):
-    """torch.xlogy: 0 where x == 0 whatever y is."""
+    """torch.xlogy: 0 where x == 0, unless y is NaN (then NaN)."""
     x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
     with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(x == 0, 0.0, x * np.log(y))
+        return np.where(x == 0, np.where(np.isnan(y), np.nan, 0.0), x * np.log(y))
+
+
+def _xlogy_dx(x, y):
+    """d xlogy(x, y) / dx as torch's autograd gives it: log(y), but 0 where x == 0 and y == 0."""
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((x == 0) & (y == 0), 0.0, np.log(y))
+
+
+def gammaln(x):
+    """lgamma as torch and C define it (scipy's gammaln(-inf) is -inf, lgamma(-inf) is +inf)."""
+    from scipy.special import gammaln as g
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x == -np.inf, np.inf, g(x))
 
 
 def gamma_log_prob(v, concentration, rate):
     """torch: torch/distributions/gamma.py log_prob
     (xlogy(concentration, rate) + xlogy(concentration - 1, value) - rate * value - lgamma)."""
-    from scipy.special import gammaln
     return _xlogy(concentration, rate) + _xlogy(concentration - 1, v) - rate * v - gammaln(concentration)
 
 
 def beta_log_prob(v, c1, c0):
     """torch: torch/distributions/beta.py log_prob = Dirichlet([c1, c0]).log_prob([v, 1 - v])
     (torch/distributions/dirichlet.py log_prob: sum xlogy(c - 1, x) + lgamma(sum c) - sum lgamma(c))."""
-    from scipy.special import gammaln
     return _xlogy(c1 - 1, v) + _xlogy(c0 - 1, 1 - v) + gammaln(c1 + c0) - gammaln(c1) - gammaln(c0)
 
 
 def poisson_log_prob(v, rate):
     """torch: torch/distributions/poisson.py log_prob (value.xlogy(rate) - rate - lgamma(value + 1))."""
-    from scipy.special import gammaln
     return _xlogy(v, rate) - rate - gammaln(v + 1)
 
 
 def binomial_logits_log_prob(v, logits, total_count):
     """pyro/distributions/torch.py:83-101 with approx_log_prob_tol = 0:
     k * logits - n * softplus(logits) + log C(n, k)   (pyro/ops/special.py log_binomial)."""
-    from scipy.special import gammaln
     n = total_count
     return v * logits - n * _softplus(logits) + gammaln(n + 1) - gammaln(v + 1) - gammaln(n - v + 1)
 
@@ -95,7 +105,6 @@ def binomial_logits_log_prob(v, logits, total_count):
 def dirichlet_log_prob(x, concentration):
     """torch: torch/distributions/dirichlet.py log_prob
     (xlogy(concentration - 1, value).sum(-1) + lgamma(concentration.sum(-1)) - lgamma(concentration).sum(-1))."""
-    from scipy.special import gammaln
     c = np.asarray(concentration, dtype=np.float64)
     return _xlogy(c - 1, x).sum(-1) + gammaln(c.sum(-1)) - gammaln(c).sum(-1)
 
@@ -108,7 +117,7 @@ def dirichlet_log_prob_grad(g, x, concentration):
     shape = np.broadcast(x, c).shape
     x, c = np.broadcast_to(x, shape), np.broadcast_to(c, shape)
     g = np.broadcast_to(np.asarray(g, dtype=np.float64), shape[:-1])[..., None]
-    return g * (c - 1) / x, g * (np.log(x) + digamma(c.sum(-1, keepdims=True)) - digamma(c))
+    return g * (c - 1) / x, g * (_xlogy_dx(c - 1, x) + digamma(c.sum(-1, keepdims=True)) - digamma(c))
 
 
 def kl_normal_normal(lq, sq, lp, sp):
@@ -159,8 +168,16 @@ def log_prob_grad(dist_id, v, a, b):
     if dist_id == 1:
         return a + z, v - _sigmoid(a), z
     if dist_id == 2:
-        den = a * a + v * v
-        return -2 * v / den, (v * v - a * a) / (a * den), z
+        # in q = v / a, or r = 1 / q where |q| > 1 (a * a + v * v overflows); torch.where's backward:
+        # zero off the support (v < 0 or NaN), NaN where q is infinite (log1p's backward 0 * inf)
+        q = v / a
+        big = np.abs(q) > 1
+        r = np.where(big, 1 / q, q)
+        den = a * (1 + r * r)
+        dv = np.where(big, -2 * r, -2 * q) / den
+        da = np.where(big, 1 - r * r, q * q - 1) / den
+        keep = np.where(np.isinf(q), np.nan, np.where(v >= 0, 1.0, 0.0))
+        return dv * keep, da * keep, z
     if dist_id == 3:
         lv = np.log(v)
         dn, da, db = normal_grad(lv, a, b)
@@ -169,7 +186,8 @@ def log_prob_grad(dist_id, v, a, b):
         return -a + z, 1 / a - v, z
     if dist_id == 5:
         dv, _, db = normal_grad(v, 0.0, a)
-        return dv, db, z
+        keep = np.where(v >= 0, 1.0, 0.0)          # torch.where's backward: zero off the support
+        return dv * keep, db * keep, z
     if dist_id == 10:
         return normal_grad(v, a, b)
     if dist_id == 11:
@@ -177,13 +195,13 @@ def log_prob_grad(dist_id, v, a, b):
     if dist_id in (6, 7, 8, 9):
         from scipy.special import digamma
         if dist_id == 6:
-            return (a - 1) / v - b, np.log(b) + np.log(v) - digamma(a) + z, a / b - v
+            return (a - 1) / v - b, _xlogy_dx(a, b) + _xlogy_dx(a - 1, v) - digamma(a) + z, a / b - v
         if dist_id == 7:
             pab = digamma(a + b)
-            return ((a - 1) / v - (b - 1) / (1 - v), np.log(v) + pab - digamma(a),
-                    np.log(1 - v) + pab - digamma(b))
+            return ((a - 1) / v - (b - 1) / (1 - v), _xlogy_dx(a - 1, v) + pab - digamma(a),
+                    _xlogy_dx(b - 1, 1 - v) + pab - digamma(b))
         if dist_id == 8:
-            return np.log(a) - digamma(v + 1), v / a - 1, z
+            return _xlogy_dx(v, a) - digamma(v + 1), v / a - 1, z
         pnk = digamma(b - v + 1)
         return (a - digamma(v + 1) + pnk, v - b * _sigmoid(a),
                 digamma(b + 1) - pnk - _softplus(a))

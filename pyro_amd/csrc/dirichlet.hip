@@ -43,6 +43,7 @@ __global__ __launch_bounds__(256) void dirichlet_lp_wave_kernel(T* __restrict__ 
 }
 
 // d_x[r,k] = g[r] (c_k - 1) / x_k ;  d_c[r,k] = g[r] (log x_k + psi(sum c) - psi(c_k))
+// (log x_k taken as 0 where c_k == 1 and x_k == 0: the derivative of torch.xlogy in its first argument)
 template <typename T>
 __global__ __launch_bounds__(256) void dirichlet_grad_thread_kernel(
     const T* __restrict__ g, ViewT<T> x, ViewT<T> c, int64_t rows, int K, T* __restrict__ dx,
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void dirichlet_grad_thread_kernel(
   for (int k = 0; k < K; ++k) {
     const T ck = c.at(r, k), xk = x.at(r, k);
     if (dx) dx[r * K + k] = gr * (ck - T(1)) / xk;
-    if (dc) dc[r * K + k] = gr * (t_log(xk) + psum - t_digamma(ck));
+    if (dc) dc[r * K + k] = gr * (t_xlogy_dx(ck - T(1), xk) + psum - t_digamma(ck));
   }
 }
 
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void dirichlet_grad_wave_kernel(
   for (int k = lane; k < K; k += 64) {
     const T ck = c.at(r, k), xk = x.at(r, k);
     if (dx) dx[r * K + k] = gr * (ck - T(1)) / xk;
-    if (dc) dc[r * K + k] = gr * (t_log(xk) + psum - t_digamma(ck));
+    if (dc) dc[r * K + k] = gr * (t_xlogy_dx(ck - T(1), xk) + psum - t_digamma(ck));
   }
 }
 
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(1024) void dirichlet_grad_block_kernel(const T* __r
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
     const T ck = c.at(r, k), xk = x.at(r, k);
     if (dx) dx[r * K + k] = gr * (ck - T(1)) / xk;
-    if (dc) dc[r * K + k] = gr * (t_log(xk) + psum - t_digamma(ck));
+    if (dc) dc[r * K + k] = gr * (t_xlogy_dx(ck - T(1), xk) + psum - t_digamma(ck));
   }
 }
 

@@ -91,9 +91,17 @@ template <typename T> struct Fam<PA_DIST_HALF_CAUCHY, T> {  // a=scale; half_cau
     return v >= T(0) ? r : -t_inf<T>();
   }
   static __device__ __forceinline__ void grad(T v, T a, T, T& dv, T& da, T& db) {
-    T den = a * a + v * v;
-    dv = -T(2) * v / den;
-    da = (v * v - a * a) / (a * den);
+    // in q = v / a, or in r = 1 / q where |q| > 1 (a * a + v * v overflows: 1e20 in f32)
+    const T q = v / a;
+    const bool big = t_abs(q) > T(1);
+    const T r = big ? T(1) / q : q, den = a * (T(1) + r * r);
+    dv = (big ? -T(2) * r : -T(2) * q) / den;
+    da = (big ? T(1) - r * r : q * q - T(1)) / den;
+    // torch.where's backward: zero off the support (v < 0, NaN); NaN where q is infinite (log1p's
+    // backward multiplies 0 by inf there)
+    const T keep = t_abs(q) == t_inf<T>() ? (T)__builtin_nan("") : (v >= T(0) ? T(1) : T(0));
+    dv *= keep;
+    da *= keep;
     db = T(0);
   }
 };
@@ -124,6 +132,9 @@ template <typename T> struct Fam<PA_DIST_HALF_NORMAL, T> {  // a=scale; half_nor
   static __device__ __forceinline__ void grad(T v, T a, T, T& dv, T& da, T& db) {
     T d0;
     Fam<PA_DIST_NORMAL, T>::grad(v, T(0), a, dv, d0, da);
+    const T keep = v >= T(0) ? T(1) : T(0);   // torch.where's backward: zero off the support
+    dv *= keep;
+    da *= keep;
     db = T(0);
   }
 };
@@ -134,9 +145,13 @@ template <> __device__ __forceinline__ float t_lgamma(float x) { return lgammaf(
 // f64: an out-of-line call -- the library lgamma inlined into the one-workgroup site kernels
 // (1024 threads, 128 VGPRs) spills every family's path, not just the Gamma-function ones
 template <> inline __device__ __noinline__ double t_lgamma(double x) { return lgamma(x); }
-// x * log(y) with the convention 0 * log(0) = 0 (torch.xlogy)
+// x * log(y) with the convention 0 * log(y) = 0 unless y is NaN (torch.xlogy)
 template <typename T> __device__ __forceinline__ T t_xlogy(T x, T y) {
-  return x == T(0) ? T(0) : x * t_log(y);
+  return x == T(0) ? (y != y ? y : T(0)) : x * t_log(y);
+}
+// d xlogy(x, y) / dx as torch's autograd defines it: log(y), but 0 where x == 0 and y == 0
+template <typename T> __device__ __forceinline__ T t_xlogy_dx(T x, T y) {
+  return (x == T(0) && y == T(0)) ? T(0) : t_log(y);
 }
 // psi(x), x > 0: upward recurrence psi(x) = psi(x+1) - 1/x into the asymptotic range, then
 //   psi(x) ~ ln x - 1/(2x) - sum_k B_2k / (2k x^2k)
@@ -171,7 +186,7 @@ template <typename T> struct Fam<PA_DIST_GAMMA, T> {  // a=concentration b=rate;
   }
   static __device__ __forceinline__ void grad(T v, T a, T b, T& dv, T& da, T& db) {
     dv = (a - T(1)) / v - b;
-    da = t_log(b) + t_log(v) - t_digamma(a);
+    da = t_xlogy_dx(a, b) + t_xlogy_dx(a - T(1), v) - t_digamma(a);
     db = a / b - v;
   }
 };
@@ -184,8 +199,8 @@ template <typename T> struct Fam<PA_DIST_BETA, T> {  // a=concentration1 b=conce
   static __device__ __forceinline__ void grad(T v, T a, T b, T& dv, T& da, T& db) {
     const T u = T(1) - v, pab = t_digamma(a + b);
     dv = (a - T(1)) / v - (b - T(1)) / u;
-    da = t_log(v) + pab - t_digamma(a);
-    db = t_log(u) + pab - t_digamma(b);
+    da = t_xlogy_dx(a - T(1), v) + pab - t_digamma(a);
+    db = t_xlogy_dx(b - T(1), u) + pab - t_digamma(b);
   }
 };
 template <typename T> struct Fam<PA_DIST_POISSON, T> {  // a=rate; torch poisson.py
@@ -193,7 +208,7 @@ template <typename T> struct Fam<PA_DIST_POISSON, T> {  // a=rate; torch poisson
     return t_xlogy(v, a) - a - t_lgamma(v + T(1));
   }
   static __device__ __forceinline__ void grad(T v, T a, T, T& dv, T& da, T& db) {
-    dv = t_log(a) - t_digamma(v + T(1));
+    dv = t_xlogy_dx(v, a) - t_digamma(v + T(1));
     da = v / a - T(1);
     db = T(0);
   }
