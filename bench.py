@@ -13,7 +13,10 @@ Multi-GPU: particles are sharded (64 per GPU, weak scaling; data replicated), gr
 with ONE flat RCCL all-reduce per step; value = world_size * steps / max-over-ranks time, i.e.
 64-particle ELBO-gradient evaluations per second over the whole job.
 
-Prints ONE JSON line (rank 0) with `roofline` and `cpu_baseline`.  The timed region replays one
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints ONE JSON line
+(rank 0) with the headline.  Everything else -- `roofline`, `cpu_baseline`, `validated`, the prearm
+variant, the other BASELINE configs and their variants, both NUTS blocks, `rccl_ranks` -- is measured
+with --full only.  The timed region replays one
 hipGraph per step; HIP events recorded inside a captured graph do not time the bracketed node on
 ROCm 7.2, so the dominant kernel's duration (`roofline.kernel_ms`) is read from the DEVICE's wall
 clock: the kernel itself records its earliest workgroup entry and latest workgroup exit
@@ -58,17 +61,19 @@ def parse():
     ap.add_argument("--plate", type=int, default=1_000_000)
     ap.add_argument("--features", type=int, default=32)
     ap.add_argument("--particles", type=int, default=64, help="particles per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: roofline (kernel clock, measured HBM), CPU "
+                         "baselines, validation on, the prearm variant, BASELINE configs 3-5 and the variants "
+                         "of configs[1] (guides, D sweep, image formats, ...), the LDA mini-batch sizes, eight "
+                         "schools, the HMM example (the variants go into bench_full.json only); the --no-* "
+                         "options and --config5-sharded select among these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-nuts", action="store_true", help="skip the secondary NUTS measurement")
     ap.add_argument("--no-others", action="store_true",
                     help="skip the one-GPU measurements of BASELINE configs 4 (LDA) and 5 (hierarchical)")
-    ap.add_argument("--full", action="store_true",
-                    help="also time the variants of configs[1] (guides, D sweep, image formats, ...), the LDA "
-                         "mini-batch sizes, eight schools and the HMM example: they go into bench_full.json, "
-                         "never into the printed line")
     ap.add_argument("--prearm", action="store_true",
                     help="headline with SVI(prearm=True) (opt-in: the caller promises to enqueue nothing between "
-                         "two steps); by default it is measured beside the headline as `with_prearm`")
+                         "two steps); with --full it is measured beside the headline as `with_prearm`")
     ap.add_argument("--no-graph", action="store_true",
                     help="eager SVI.step (Python handlers + one launch per kernel) instead of the "
                          "captured hipGraph step")
@@ -87,7 +92,7 @@ def parse():
                     help="also time BASELINE configs[4] with the PLATE sharded over the ranks (SURVEY "
                          "8e variant 2): rows / world per GPU, the same particles everywhere, the "
                          "likelihood scaled to the full plate, one flat RCCL gradient all-reduce "
-                         "(default: on when launched with more than one rank)")
+                         "(with --full; default: on when launched with more than one rank)")
     ap.add_argument("--config5-rows", type=int, default=10_000_000)
     ap.add_argument("--config5-groups", type=int, default=1000)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -596,10 +601,12 @@ def compact(out):
     line = _pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                  "scaling", "vs_baseline", "dtype", "data", "rccl_ranks", "replay")
     line["config"] = out["config"]
-    rf = out["roofline"]
-    line["roofline"] = _pick(rf, "bound", "kernel", "kernel_ms", "kernel_ms_eager", "kernel_ms_rocprof", "achieved",
-                             "peak", "unit", "frac", "frac_rocprof", "traffic", "algorithmic_bytes_per_launch")
-    line["roofline"]["traffic_source"] = _file_only(rf.get("traffic_source"))
+    rf = out.get("roofline")                   # (--full only)
+    if rf:
+        line["roofline"] = _pick(rf, "bound", "kernel", "kernel_ms", "kernel_ms_eager", "kernel_ms_rocprof",
+                                 "achieved", "peak", "unit", "frac", "frac_rocprof", "traffic",
+                                 "algorithmic_bytes_per_launch")
+        line["roofline"]["traffic_source"] = _file_only(rf.get("traffic_source"))
     cb = out.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = _pick(cb, "value", "unit", "cores", "kind")
@@ -717,7 +724,8 @@ def main():
     if world > 1:
         optim = pyro.optim.RcclOptimizer(optim)
     use_graph = not args.no_graph
-    # the dominant kernel's own clock stamps (a launch argument: created before the capture)
+    # the dominant kernel's own clock stamps (a launch argument: created before the capture, and in a plain run
+    # too, so that the timed steps replay the same captured step with and without --full)
     clock = kernels.GlmDeviceClock(dev) if on_gpu else None
     # The headline is the reference's constructor and nothing else: SVI(model, guide, optim, loss).  With
     # device tensors as arguments such an SVI captures its step into a hipGraph by itself (after 3 eager
@@ -801,7 +809,7 @@ def main():
     headline_f16 = headline_planes and kernels.glm_planes_format() == kernels.GLM_PLANES_F16X2
     prearmed = bool(prearm and graphed and next(iter(svi._graphs.values())).gate is not None)
     unarmed = None
-    if prearmed:
+    if prearmed and args.full:
         # the same captured step with every replay launched by its own step() call
         svi.disarm()
         nu = min(args.steps, 300)
@@ -818,7 +826,7 @@ def main():
                    "note": "the same capture after SVI.disarm(): the host launches each replay when "
                            "step() is called (what SVI(..., prearm=False) runs)"}
     clock_ms = []
-    if graphed and not graphed_events:
+    if graphed and not graphed_events and args.full:
         # the kernel's duration inside the graph, from its own stamps on the device clock
         for _ in range(20):
             clock.arm()
@@ -832,7 +840,7 @@ def main():
             svi._eager_step(X, y)
         torch.cuda.synchronize()
     armed = None
-    if world == 1 and graphed and not prearmed and on_gpu:
+    if world == 1 and graphed and not prearmed and on_gpu and args.full:
         # the opt-in variant beside the headline: SVI(prearm=True) on the same guide / optimizer
         svi_p = SVI(examples.logreg_model, guide, optim,
                     Trace_ELBO(num_particles=P, vectorize_particles=True, max_plate_nesting=1),
@@ -858,7 +866,7 @@ def main():
                          "writes)"}
         svi_p.release()
     validated = None
-    if world == 1 and graphed:
+    if world == 1 and graphed and args.full:
         # the same measurement with validation switched on (it runs in the eager steps before the
         # capture; the captured step is the same graph)
         pyro.enable_validation(True)
@@ -886,6 +894,7 @@ def main():
         t = torch.tensor(block_s, device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)          # max over ranks
         block_s = [float(v) for v in t.cpu()]
+    if world > 1 and args.full:
         # how many ranks the communicator actually holds: a sum of ones through the same backend the
         # gradient all-reduce uses (not the WORLD_SIZE environment variable)
         ones = torch.ones((1,), device=dev, dtype=torch.float32)
@@ -896,7 +905,7 @@ def main():
     sharded5 = None
     if args.config5_sharded is None:
         args.config5_sharded = world > 1                   # (both SURVEY 8e variants on a multi-GPU run)
-    if args.config5_sharded:
+    if args.config5_sharded and args.full:
         # every rank holds rows / world rows (its own synthetic shard), draws the SAME particles (one
         # seed), scores its rows scaled by `world`, and the flat gradient is averaged over the ranks
         n_loc = args.config5_rows // world
@@ -932,9 +941,9 @@ def main():
                                 "the same %d particles on every rank, likelihood scaled by the world size, "
                                 "flat gradient all-reduce (mean)" % (n_loc * world, args.config5_groups, P)}
         pyro.clear_param_store()
-    nuts = None if args.no_nuts else bench_nuts(dev, rank, world, args)
+    nuts = None if args.no_nuts or not args.full else bench_nuts(dev, rank, world, args)
     model_nuts = None
-    if not args.no_model_nuts:
+    if args.full and not args.no_model_nuts:
         try:
             model_nuts = bench_model_nuts(dev, rank, world, args)
         except Exception as e:  # noqa: BLE001  (a secondary measurement must not kill the headline)
@@ -942,7 +951,7 @@ def main():
                 raise
             model_nuts = {"error": "%s: %s" % (type(e).__name__, e)}
     others = None
-    if world == 1 and not args.no_others:
+    if world == 1 and args.full and not args.no_others:
         # BASELINE configs[3] and configs[4] (one GPU's share) -- reported, not the headline value
         from tools import bench_configs
         others = {}
@@ -966,45 +975,44 @@ def main():
                               "assignment enumerated: likelihood against every component + logsumexp + plate sum "
                               "+ all gradients in one pass over the data (csrc/mixture.hip); graphed SVI.step")
             others["gmm_enumerated"] = rg
-            if args.full:
-                rg0 = bench_configs.config_gmm(dev, leaf=False)
-                rg0["workload"] = "the same mixture with its [K, N] likelihood materialised (round 3's elimination)"
-                others["gmm_enumerated_materialised"] = rg0
-                for bs in (32, 4096):      # the mini-batch variants SURVEY 8(d) lists
-                    rb = bench_configs.config4(dev, steps=30, batch_size=bs)
-                    rb["workload"] = ("examples/lda.py with batch_size=%d of 1e5 documents per step (a fresh "
-                                      "sub-sampled word matrix every step: LDS-atomic factor kernel), "
-                                      "graphed SVI.step" % bs)
-                    others["config4_lda_batch%d" % bs] = rb
-                r1 = bench_configs.config1(dev)
-                r1["workload"] = ("BASELINE configs[0]: eight schools, Trace_ELBO, 1 particle, Adam; graphed "
-                                  "SVI.step (the reference's own CPU-runnable case: ~58 steps/s there)")
-                others["config1_eight_schools"] = r1
-                rh = bench_configs.config_hmm(dev, steps=10, graph=True)
-                rh["workload"] = ("examples/hmm.py model_1 at its JSB-chorales size (229 sequences x 129 "
-                                  "steps, 16 hidden states, 88 tones), TraceEnum_ELBO under pyro.markov, "
-                                  "chain summed out by pa_logchain_fwd_bwd, graphed SVI.step")
-                others["hmm_example"] = rh
-                rv = bench_configs.config_hmm_vectorised(dev)
-                rv["workload"] = ("the same HMM likelihood with time vectorised in one DiscreteHMM site "
-                                  "(examples/hmm.py model_7's construction): one pa_logchain_fwd_bwd launch "
-                                  "for all sequences, graphed SVI.step")
-                others["hmm_example_vectorised"] = rv
-                r2m = bench_configs.config2_variant(dev, "mvn")
-                r2m["workload"] = ("BASELINE configs[1] with AutoMultivariateNormal (the second guide "
-                                   "SURVEY 8d names), 64 particles, graphed SVI.step")
-                others["config2_automultivariatenormal"] = r2m
-                r2p = bench_configs.config2_variant(dev, "normal", P=1)
-                r2p["workload"] = ("BASELINE configs[1] at the reference's default num_particles=1: "
-                                   "few-particle vector-ALU GLM kernel (HBM-bound), graphed SVI.step")
-                others["config2_one_particle"] = r2p
-                r2e = bench_configs.config2_variant(dev, "normal", model=examples.logreg_model_explicit)
-                r2e["workload"] = ("BASELINE configs[1] with the logits spelled as dist.linear_logits(X, w, b) "
-                                   "and hoisted prior constants instead of the reference's model text "
-                                   "(same kernels, two fill launches fewer)")
-                others["config2_explicit_linear_logits"] = r2e
+            rg0 = bench_configs.config_gmm(dev, leaf=False)
+            rg0["workload"] = "the same mixture with its [K, N] likelihood materialised (round 3's elimination)"
+            others["gmm_enumerated_materialised"] = rg0
+            for bs in (32, 4096):      # the mini-batch variants SURVEY 8(d) lists
+                rb = bench_configs.config4(dev, steps=30, batch_size=bs)
+                rb["workload"] = ("examples/lda.py with batch_size=%d of 1e5 documents per step (a fresh "
+                                  "sub-sampled word matrix every step: LDS-atomic factor kernel), "
+                                  "graphed SVI.step" % bs)
+                others["config4_lda_batch%d" % bs] = rb
+            r1 = bench_configs.config1(dev)
+            r1["workload"] = ("BASELINE configs[0]: eight schools, Trace_ELBO, 1 particle, Adam; graphed "
+                              "SVI.step (the reference's own CPU-runnable case: ~58 steps/s there)")
+            others["config1_eight_schools"] = r1
+            rh = bench_configs.config_hmm(dev, steps=10, graph=True)
+            rh["workload"] = ("examples/hmm.py model_1 at its JSB-chorales size (229 sequences x 129 "
+                              "steps, 16 hidden states, 88 tones), TraceEnum_ELBO under pyro.markov, "
+                              "chain summed out by pa_logchain_fwd_bwd, graphed SVI.step")
+            others["hmm_example"] = rh
+            rv = bench_configs.config_hmm_vectorised(dev)
+            rv["workload"] = ("the same HMM likelihood with time vectorised in one DiscreteHMM site "
+                              "(examples/hmm.py model_7's construction): one pa_logchain_fwd_bwd launch "
+                              "for all sequences, graphed SVI.step")
+            others["hmm_example_vectorised"] = rv
+            r2m = bench_configs.config2_variant(dev, "mvn")
+            r2m["workload"] = ("BASELINE configs[1] with AutoMultivariateNormal (the second guide "
+                               "SURVEY 8d names), 64 particles, graphed SVI.step")
+            others["config2_automultivariatenormal"] = r2m
+            r2p = bench_configs.config2_variant(dev, "normal", P=1)
+            r2p["workload"] = ("BASELINE configs[1] at the reference's default num_particles=1: "
+                               "few-particle vector-ALU GLM kernel (HBM-bound), graphed SVI.step")
+            others["config2_one_particle"] = r2p
+            r2e = bench_configs.config2_variant(dev, "normal", model=examples.logreg_model_explicit)
+            r2e["workload"] = ("BASELINE configs[1] with the logits spelled as dist.linear_logits(X, w, b) "
+                               "and hoisted prior constants instead of the reference's model text "
+                               "(same kernels, two fill launches fewer)")
+            others["config2_explicit_linear_logits"] = r2e
             # "loss_and_grads only" beside the full step, the D sweep, and the
-            # exact three-plane bf16 image beside the default two-plane f16 one on every run
+            # exact three-plane bf16 image beside the default two-plane f16 one on every full run
             r2g = bench_configs.config2_variant(dev, "normal", no_update=True)
             r2g["workload"] = ("BASELINE configs[1], loss_and_grads only: the captured step without the "
                                "optimizer update (guide draw, fused ELBO gradient, guide backward, gradient "
@@ -1015,52 +1023,22 @@ def main():
                                "split exactly, 6 piece products): the headline's arithmetic without the "
                                "2^-22 representation error of the two-plane f16 image")
             others["config2_bf16x3_exact_split"] = r2x
-            if args.full:
-                for Dv in (8, 64, 128):
-                    rd = bench_configs.config2_variant(dev, "normal", D=Dv, steps=30)
-                    rd["workload"] = ("BASELINE configs[1] at D=%d (SURVEY 8d sweep): %s" % (
-                        Dv, "plane-image kernel" if Dv <= 32 else
-                        "plane-image kernel with %d feature tiles of 32 columns (csrc/glm_planes16d.h; until "
-                        "round 4 D > 32 split X on the fly in two passes)" % (2 if Dv <= 64 else 4)))
-                    others["config2_D%d" % Dv] = rd
-                r2u = bench_configs.config2_variant(dev, "normal", lazy_matmul=False, steps=20)
-                r2u["workload"] = ("BASELINE configs[1], the reference's model text with the lazy recognition "
-                                   "of w @ X.t() switched OFF: [P, N] logits materialised by rocBLAS, "
-                                   "log-prob / gradient by the fused site kernels, rocBLAS for dw")
-                others["config2_materialised_logits"] = r2u
+            for Dv in (8, 64, 128):
+                rd = bench_configs.config2_variant(dev, "normal", D=Dv, steps=30)
+                rd["workload"] = ("BASELINE configs[1] at D=%d (SURVEY 8d sweep): %s" % (
+                    Dv, "plane-image kernel" if Dv <= 32 else
+                    "plane-image kernel with %d feature tiles of 32 columns (csrc/glm_planes16d.h; until "
+                    "round 4 D > 32 split X on the fly in two passes)" % (2 if Dv <= 64 else 4)))
+                others["config2_D%d" % Dv] = rd
+            r2u = bench_configs.config2_variant(dev, "normal", lazy_matmul=False, steps=20)
+            r2u["workload"] = ("BASELINE configs[1], the reference's model text with the lazy recognition "
+                               "of w @ X.t() switched OFF: [P, N] logits materialised by rocBLAS, "
+                               "log-prob / gradient by the fused site kernels, rocBLAS for dw")
+            others["config2_materialised_logits"] = r2u
         except Exception as e:  # noqa: BLE001  (secondary measurements must not kill the headline)
             others["error"] = "%s: %s" % (type(e).__name__, e)
         pyro.clear_param_store()
     if rank == 0:
-        kern_ms_eager = sum(kern_ms_list) / len(kern_ms_list) if kern_ms_list else timer.mean_ms()
-        kern_ms = sum(clock_ms) / len(clock_ms) if clock_ms else kern_ms_eager
-        gemm_flops = 4.0 * P * N * D                      # two [P,D]x[D,N]-shaped contractions
-        alg_bytes = N * (4 * D + 4)                        # X (f32) + y (f32), read once
-        achieved_tflops = gemm_flops / (kern_ms * 1e-3) / 1e12
-        # counter-measured HBM bytes per launch and the in-graph duration of the dominant kernel
-        # come from the rocprofv3 passes over this same command (tools/prof.sh), committed under
-        # profiles/: they cannot be collected from inside the run
-        traffic = rocprof_ms = None
-        traffic_src = None
-        tpath = latest_profile("traffic.json")
-        if tpath is None:
-            traffic_src = "none: no profiles/r%02d_traffic.json committed this round (earlier rounds' files are refused)" % ROUND
-        if tpath is not None:
-            try:
-                tj = json.load(open(tpath))
-                # ... and only for the kernel family that is running now
-                running = ("glm_planes_f16_kernel" if headline_f16 else "glm_planes_kernel") if headline_planes \
-                    else "glm_bernoulli_bf16_kernel"
-                if running in str(tj.get("kernel", "")):
-                    traffic, rocprof_ms = tj.get("hbm_bytes_per_launch"), tj.get("kernel_ms_in_graph")
-                    traffic_src = "profiles/%s (%s)" % (os.path.basename(tpath), tj.get("how", ""))
-                else:
-                    traffic_src = "refused: profiles/%s measured %s, this run launches %s" % (
-                        os.path.basename(tpath), str(tj.get("kernel"))[:60], running)
-            except Exception:
-                traffic = None
-        planes, f16 = headline_planes, headline_f16      # (noted right after the timed region)
-        n_prod = 3 if f16 else 6                       # piece products per element product
         out = {
             "metric": "ELBO-grad steps/sec (SVI)", "value": world * args.steps / elapsed,
             "unit": "ELBO-grad steps/s (64 particles x 1e6-row plate per step)",
@@ -1076,51 +1054,83 @@ def main():
                                        ("one hipGraph replay per step" + (", prearm=True" if prearmed else ""))
                                        if graphed else "eager launches")),
                        "parallelism": "particles sharded x%d, flat RCCL grad all-reduce" % world},
-            # SURVEY 8(d): the plate scan is priced against HBM (algorithmic bytes = X and y once)
-            "roofline": {"bound": "hbm", "achieved": alg_bytes / (kern_ms * 1e-3) / 1e9,
-                         "peak": PEAK_HBM_TBS * 1e3, "unit": "GB/s",
-                         "frac": alg_bytes / (kern_ms * 1e-3) / 1e12 / PEAK_HBM_TBS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": ("glm_planes_f16_kernel" if f16 else "glm_planes_kernel") if planes
-                         else "glm_bernoulli_bf16_kernel",
-                         "kernel_ms": kern_ms,
-                         "kernel_ms_source": ("the kernel's own stamps on the device wall clock "
-                                              "(earliest workgroup entry -> latest workgroup exit), "
-                                              "mean of %d replays of the captured step right after "
-                                              "the timed region" % len(clock_ms)) if clock_ms else
-                                             "HIP events around the kernel on its launch stream",
-                         "kernel_ms_eager": kern_ms_eager,
-                         "kernel_ms_rocprof": rocprof_ms,
-                         "frac_rocprof": (alg_bytes / (rocprof_ms * 1e-3) / 1e12 / PEAK_HBM_TBS)
-                         if rocprof_ms else None,
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "arithmetic": ("f32-class: every f32 operand as two power-of-two-scaled f16 "
-                                        "pieces (2^-22 relative), the 3 piece products of order >= "
-                                        "2^-11 on the f16 matrix cores, f32 accumulation; error "
-                                        "against float64 equal to an f32 evaluation's "
-                                        "(tests/test_kernels_gpu.py::test_glm_planes_f16_is_f32_class; "
-                                        "PYRO_AMD_GLM_PLANES=bf16x3 selects the exact 3-piece image)")
-                         if f16 else
-                                       "f32-equivalent: every f32 operand split exactly into 3 bf16 "
-                                       "pieces, the 6 piece products of order >= 2^-16 on the bf16 "
-                                       "matrix cores, f32 accumulation",
-                         # the other two resources the kernel uses, for the same duration:
-                         "mfma_piece_TFLOPs": n_prod * gemm_flops / (kern_ms * 1e-3) / 1e12,
-                         "frac_16bit_mfma": n_prod * gemm_flops / (kern_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS,
-                         "f32_equivalent_TFLOPs": achieved_tflops,
-                         "binding_resource": BINDING_F16 if f16 else BINDING_BF16},
-            "rccl_ranks": rccl_ranks,      # measured: all_reduce(SUM) of ones over the process group
         }
-        if world == 1 and on_gpu:
-            try:
-                out["roofline"]["measured_hbm"] = measured_hbm(dev)
-            except Exception as e:  # noqa: BLE001
-                out["roofline"]["measured_hbm"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(N, D, P, args.cpu_budget_s)
-            ref = reference_cpu_record()
-            if ref is not None:
-                out["cpu_baseline"]["reference"] = ref
+        if args.full:
+            kern_ms_eager = sum(kern_ms_list) / len(kern_ms_list) if kern_ms_list else timer.mean_ms()
+            kern_ms = sum(clock_ms) / len(clock_ms) if clock_ms else kern_ms_eager
+            gemm_flops = 4.0 * P * N * D                      # two [P,D]x[D,N]-shaped contractions
+            alg_bytes = N * (4 * D + 4)                        # X (f32) + y (f32), read once
+            achieved_tflops = gemm_flops / (kern_ms * 1e-3) / 1e12
+            # counter-measured HBM bytes per launch and the in-graph duration of the dominant kernel
+            # come from the rocprofv3 passes over this same command (tools/prof.sh), committed under
+            # profiles/: they cannot be collected from inside the run
+            traffic = rocprof_ms = None
+            traffic_src = None
+            tpath = latest_profile("traffic.json")
+            if tpath is None:
+                traffic_src = ("none: no profiles/r%02d_traffic.json committed this round (earlier rounds' files "
+                               "are refused)" % ROUND)
+            if tpath is not None:
+                try:
+                    tj = json.load(open(tpath))
+                    # ... and only for the kernel family that is running now
+                    running = ("glm_planes_f16_kernel" if headline_f16 else "glm_planes_kernel") if headline_planes \
+                        else "glm_bernoulli_bf16_kernel"
+                    if running in str(tj.get("kernel", "")):
+                        traffic, rocprof_ms = tj.get("hbm_bytes_per_launch"), tj.get("kernel_ms_in_graph")
+                        traffic_src = "profiles/%s (%s)" % (os.path.basename(tpath), tj.get("how", ""))
+                    else:
+                        traffic_src = "refused: profiles/%s measured %s, this run launches %s" % (
+                            os.path.basename(tpath), str(tj.get("kernel"))[:60], running)
+                except Exception:
+                    traffic = None
+            planes, f16 = headline_planes, headline_f16      # (noted right after the timed region)
+            n_prod = 3 if f16 else 6                       # piece products per element product
+            # SURVEY 8(d): the plate scan is priced against HBM (algorithmic bytes = X and y once)
+            rf = {"bound": "hbm", "achieved": alg_bytes / (kern_ms * 1e-3) / 1e9,
+                  "peak": PEAK_HBM_TBS * 1e3, "unit": "GB/s",
+                  "frac": alg_bytes / (kern_ms * 1e-3) / 1e12 / PEAK_HBM_TBS,
+                  "traffic": traffic, "traffic_source": traffic_src,
+                  "kernel": ("glm_planes_f16_kernel" if f16 else "glm_planes_kernel") if planes
+                  else "glm_bernoulli_bf16_kernel",
+                  "kernel_ms": kern_ms,
+                  "kernel_ms_source": ("the kernel's own stamps on the device wall clock "
+                                       "(earliest workgroup entry -> latest workgroup exit), "
+                                       "mean of %d replays of the captured step right after "
+                                       "the timed region" % len(clock_ms)) if clock_ms else
+                                      "HIP events around the kernel on its launch stream",
+                  "kernel_ms_eager": kern_ms_eager,
+                  "kernel_ms_rocprof": rocprof_ms,
+                  "frac_rocprof": (alg_bytes / (rocprof_ms * 1e-3) / 1e12 / PEAK_HBM_TBS)
+                  if rocprof_ms else None,
+                  "algorithmic_bytes_per_launch": alg_bytes,
+                  "arithmetic": ("f32-class: every f32 operand as two power-of-two-scaled f16 "
+                                 "pieces (2^-22 relative), the 3 piece products of order >= "
+                                 "2^-11 on the f16 matrix cores, f32 accumulation; error "
+                                 "against float64 equal to an f32 evaluation's "
+                                 "(tests/test_kernels_gpu.py::test_glm_planes_f16_is_f32_class; "
+                                 "PYRO_AMD_GLM_PLANES=bf16x3 selects the exact 3-piece image)")
+                  if f16 else
+                                "f32-equivalent: every f32 operand split exactly into 3 bf16 "
+                                "pieces, the 6 piece products of order >= 2^-16 on the bf16 "
+                                "matrix cores, f32 accumulation",
+                  # the other two resources the kernel uses, for the same duration:
+                  "mfma_piece_TFLOPs": n_prod * gemm_flops / (kern_ms * 1e-3) / 1e12,
+                  "frac_16bit_mfma": n_prod * gemm_flops / (kern_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS,
+                  "f32_equivalent_TFLOPs": achieved_tflops,
+                  "binding_resource": BINDING_F16 if f16 else BINDING_BF16}
+            out["roofline"] = rf
+            out["rccl_ranks"] = rccl_ranks      # measured: all_reduce(SUM) of ones over the process group
+            if world == 1 and on_gpu:
+                try:
+                    out["roofline"]["measured_hbm"] = measured_hbm(dev)
+                except Exception as e:  # noqa: BLE001
+                    out["roofline"]["measured_hbm"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(N, D, P, args.cpu_budget_s)
+                ref = reference_cpu_record()
+                if ref is not None:
+                    out["cpu_baseline"]["reference"] = ref
         if validated is not None:
             out["validated"] = validated
         if unarmed is not None:

@@ -114,6 +114,26 @@ def test_bench_torchrun_path_prints_one_line_with_two_ranks(tmp_path):
 
 
 
+@pytest.mark.timeout(600)
+def test_plain_bench_run_prints_the_headline_and_measures_nothing_else(tmp_path):
+    """`bench.py --gpus 2 --steps 3` without --full: the timed steps and the headline line, and none of what
+    --full measures -- no NUTS blocks (kept in the host run by PYRO_AMD_BENCH_CPU_NUTS), no sharded config 5,
+    no rccl_ranks check, no roofline."""
+    import json
+    outs = _run(dw.bench_worker, 2, (3, True, False), tmp_path, "bench2plain")
+    lines = [ln for ln in outs[0]["stdout"].splitlines() if ln.strip()]
+    assert len(lines) == 1, outs[0]["stdout"]
+    rec = json.loads(lines[0])
+    assert rec["metric"].startswith("ELBO-grad steps/sec") and rec["value"] > 0
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1
+    assert rec["unit"] and rec["dtype"] == "f32" and rec["higher_is_better"] is True
+    assert abs(rec["ms_per_step"] - 2 * 1e3 / rec["value"]) < 1e-3 * rec["ms_per_step"]
+    for k in ("roofline", "rccl_ranks", "cpu_baseline", "validated", "with_prearm", "other_configs", "secondary",
+              "secondary_model_nuts"):
+        assert k not in rec, k
+    assert outs[1]["stdout"].strip() == ""
+
+
 @pytest.mark.timeout(900)
 def test_bench_with_eight_ranks_including_both_nuts_blocks(tmp_path):
     """`bench.py --gpus 8 --steps 3` as the driver launches it on an 8-GPU node, on host tensors over gloo

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"
 OUT=gpurun_out/nuts_pmc; rm -rf $OUT; mkdir -p $OUT
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o b -- python bench.py --steps 5 --warmup 5 --no-others --no-model-nuts --no-cpu-baseline > $OUT/$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o b -- python bench.py --full --steps 5 --warmup 5 --no-others --no-model-nuts --no-cpu-baseline > $OUT/$C.log 2>&1
 done
 python - "$OUT" <<'PY'
 import csv, glob, json, sys, collections

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"
 OUT=gpurun_out/pmc_nuts_${1:-x}; rm -rf $OUT; mkdir -p $OUT
 for C in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_INSTS_BRANCH SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS"; do
   N=$(echo $C | tr ' ' '_' | cut -c1-30)
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$N -o n -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-others > $OUT/$N.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$N -o n -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-others > $OUT/$N.log 2>&1
 done
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections, os
