@@ -1080,6 +1080,28 @@ int pa_mixture_diag_normal_fwd_bwd(int dtype, const void* x, int64_t N, int D, i
                                    int64_t scale_stride_k, int64_t scale_stride_d, int64_t scale_batch_stride,
                                    void* workspace, size_t workspace_bytes, double* out_padded, pa_stream_t stream);
 
+/* ---- csrc/mixture_mvn.hip: the mixture leaf for a full-covariance MultivariateNormal observation ----------------
+ * Replaces, for `MultivariateNormal(locs[z], scale_tril=L[z])` observed under the data plate with z enumerated
+ * (pyro/infer/traceenum_elbo.py:112-214, pyro/ops/contract.py:79-160): torch's MultivariateNormal.log_prob over the
+ * [K, N, D] difference x - loc with its batched triangular solve (torch/distributions/multivariate_normal.py
+ * log_prob, _batch_mahalanobis), the logsumexp over K, the plate sum, and the autograd duals of all of them.
+ * With W = L^-1 (lower triangular, only its lower triangle is read), d = x_n - loc_k, z = W_k d:
+ *   S[b] = sum_n log sum_k exp(a[b][k] + sum_i log W[b][k][i][i] - D/2 log 2 pi - |z|^2 / 2),  K <= 64, D <= 64,
+ * and with r_nk = softmax_k the statistics of the gradients: R[b][k] = sum_n r_nk (= dS/da), m[b][k] = sum_n r_nk z
+ * and G[b][k] = sum_n r_nk z d^T (lower triangle; dS/dloc_k = W_k^T m_k, dS/dW_k = diag(R_k / W_k,ii) - G_k).
+ * x [N, D] row-major; a[b][k] = a[b * a_batch_stride + k]; loc[b][k][i] = loc[b * loc_batch_stride +
+ * k * loc_stride_k + i]; W[b][k][i][j] = w[b * w_batch_stride + k * w_stride_k + i * D + j] (stride 0: shared).
+ * out[b * J + ...], J = pa_mixture_mvn_layout(K, D) = 1 + K + K D + K D^2 doubles: [0] = S, [1 + k] = R_k,
+ * [1 + K + k D + i] = m_ki, [1 + K + K D + (k D + i) D + j] = G_kij (zero above the diagonal).  row_lse: B N values
+ * of `dtype` (the rows' logsumexp between the launches).  Workspace: pa_mixture_mvn_workspace(K, D, B) bytes, at
+ * most 34.1 MB at K = D = 64, B = 1.  Three launches, no host synchronisation, bit-reproducible. */
+int64_t pa_mixture_mvn_layout(int K, int D);
+size_t pa_mixture_mvn_workspace(int K, int D, int64_t B);
+int pa_mixture_mvn_fwd_bwd(int dtype, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                           int64_t a_batch_stride, const void* loc, int64_t loc_stride_k, int64_t loc_batch_stride,
+                           const void* w, int64_t w_stride_k, int64_t w_batch_stride, void* row_lse,
+                           void* workspace, size_t workspace_bytes, double* out, pa_stream_t stream);
+
 /* ---- csrc/replay.hip: a captured step that is a short chain of kernels, launched as kernels ----------------
  * Replaces nothing of the reference's (its SVI.step, pyro/infer/svi.py:134-162, re-runs the model): it is the
  * replay path of this package's captured step, opt-in on the host side: measured on config 2 a step that waits for

@@ -30,6 +30,7 @@ import torch
 from ..distributions.fused import grad_sink as _grad_sink
 
 from .. import kernels, poutine
+from ..distributions.base import ExpandedDistribution
 from ..distributions.util import scale_and_mask
 from ..ops.contract import LazyGather, Term, _eliminate, align, contract_tensor_tree, pack
 from ..poutine.util import prune_subsample_sites
@@ -126,6 +127,9 @@ def _lazy_family(site, first_enum_dim):
     fn, value = site["fn"], site["value"]
     if not contract.FUSED_MIXTURE or not site["is_observed"] or not (site["mask"] is None or site["mask"] is True):
         return None
+    base = fn.base_dist if isinstance(fn, ExpandedDistribution) else fn
+    if isinstance(base, torch.distributions.MultivariateNormal):
+        return _lazy_mvn(site, first_enum_dim)
     ev = tuple(getattr(fn, "event_shape", ()))
     if not isinstance(value, torch.Tensor) or value.dim() != 1 + len(ev) or value.requires_grad \
             or value.dtype not in (torch.float32, torch.float64) or not kernels.on_device(value):
@@ -195,6 +199,75 @@ def _lazy_family(site, first_enum_dim):
         return None
     return site["infer"]["_dim_to_id"][edim], contract.LazyFamily(ent[0], value, K, params[0], params[1], packed,
                                                                   batch_dim, B, D)
+
+
+def _unexpanded(p):
+    """``p`` without the stretch of its stride-0 dims (torch's MultivariateNormal keeps ``loc`` expanded to the batch
+    shape): the same memory seen through its view base, so that the gradient flows into that base directly --
+    through the expanded view it would be reduced from a tensor of the expanded size."""
+    if all(s_ == 1 or st != 0 for s_, st in zip(p.shape, p.stride())):
+        return p
+    b = p._base if p._base is not None else p
+    shape = [1 if st == 0 else s_ for s_, st in zip(p.shape, p.stride())]
+    return b.as_strided(shape, p.stride(), p.storage_offset())
+
+
+def _lazy_mvn(site, first_enum_dim):
+    """``MultivariateNormal(locs[z], scale_tril=L[z])`` (or ``covariance_matrix`` / ``precision_matrix``; or an
+    ExpandedDistribution of one) observed with data [N, D] under the data plate (dim -1) and at most one outer plate,
+    its loc and scale_tril varying along ONE enumerated dim (and the outer plate) only: the [K, (B,) N] factor kept as
+    (data, loc, scale_tril) for csrc/mixture_mvn.hip.  -> (enum id, LazyMvn) or None (the generic path)."""
+    from ..ops import contract
+    fn, value = site["fn"], site["value"]
+    base = fn.base_dist if isinstance(fn, ExpandedDistribution) else fn
+    D = base.event_shape[0]
+    if not isinstance(value, torch.Tensor) or value.dim() != 2 or value.shape[1] != D or value.requires_grad \
+            or value.dtype not in (torch.float32, torch.float64) or not kernels.on_device(value):
+        return None
+    if D < 1 or D > kernels.MIXTURE_MVN_MAX_D:
+        return None
+    plate_dims = sorted(f.dim for f in site["cond_indep_stack"] if f.vectorized)
+    if not plate_dims or plate_dims[-1] != -1 or len(plate_dims) > 2:
+        return None
+    bs = tuple(fn.batch_shape)
+    if len(bs) < 2 or bs[-1] not in (1, value.shape[0]):
+        return None
+    nb = len(bs)
+    batch_dim = plate_dims[0] if len(plate_dims) == 2 else None
+    if batch_dim is not None and -batch_dim > nb:
+        batch_dim = None
+    nz = [i for i, s_ in enumerate(bs[:-1]) if s_ > 1 and i - nb != batch_dim]
+    if len(nz) != 1 or (batch_dim is not None and nz[0] - nb > batch_dim):
+        return None
+    edim = nz[0] - nb
+    if edim > first_enum_dim or edim not in site["infer"].get("_dim_to_id", {}):
+        return None
+    K = bs[nz[0]]
+    B = 1 if batch_dim is None else bs[batch_dim]
+    if batch_dim is not None and B == 1:
+        batch_dim = None
+    if K > kernels.MIXTURE_MAX_K:
+        return None
+    params = []
+    for p, ne in ((_unexpanded(base.loc), 1), (base._unbroadcasted_scale_tril, 2)):
+        if p.dtype != value.dtype or not kernels.on_device(p) or p.dim() > nb + ne:
+            return None
+        shp = (1,) * (nb + ne - p.dim()) + tuple(p.shape)
+        if shp[nb:] != (D,) * ne:
+            return None
+        for i, s_ in enumerate(shp[:nb]):
+            d = i - nb
+            if not (s_ == 1 or (d == edim and s_ == K) or (batch_dim is not None and d == batch_dim and s_ == B)):
+                return None                   # varies along the data plate (or another dim): the generic path
+        Kp = shp[nz[0]]
+        Bp = 1 if batch_dim is None else shp[nb + batch_dim]
+        params.append(p.reshape((Kp, Bp) + (D,) * ne))
+
+    def packed():
+        lp = fn.log_prob(value, *site["args"], **site["kwargs"])
+        return _packed(site, lp, first_enum_dim).tensor
+
+    return site["infer"]["_dim_to_id"][edim], contract.LazyMvn(value, K, params[0], params[1], packed, batch_dim, B)
 
 
 class TraceEnum_ELBO(ELBO):

@@ -2014,6 +2014,44 @@ def mixture_diag_normal_fwd_bwd(x, a, loc, scale):
     return S, da, dl, dc
 
 
+MIXTURE_MVN_MAX_D = 64
+
+
+def mixture_mvn_fwd_bwd(x, a, loc, W):
+    """The mixture leaf for a full-covariance MultivariateNormal over D <= 64 features (pa_mixture_mvn_fwd_bwd):
+    x [N, D]; a [B, K]; loc [B | 1, K | 1, D]; W [B | 1, K | 1, D, D] = the inverse of the scale_tril (lower
+    triangular), all contiguous and of x's dtype.  -> (S [B], R [B, K], m [B, K, D], G [B, K, D, D]) in float64 on
+    the device, per (b, k): S = sum_n logsumexp_k log N(x_n | loc_k, (W_k^T W_k)^-1) + a_k, R = dS/da,
+    m = sum_n r_nk W_k (x_n - loc_k), G = sum_n r_nk W_k (x_n - loc_k) (x_n - loc_k)^T (zero above the diagonal)."""
+    _require_gpu(x, a, loc, W)
+    N, D = x.shape
+    B, K = a.shape
+    assert x.is_contiguous() and a.is_contiguous() and loc.is_contiguous() and W.is_contiguous()
+    assert loc.dim() == 3 and W.dim() == 4 and a.dtype == x.dtype == loc.dtype == W.dtype
+    lib = _lib.load()
+    J = lib.pa_mixture_mvn_layout(K, D)
+    nbytes = lib.pa_mixture_mvn_workspace(K, D, B)
+    if J == 0 or nbytes == 0:
+        raise Unsupported("pyro_amd: mixture_mvn_fwd_bwd needs K <= %d, D <= %d, B <= 65535 (K=%d, D=%d, B=%d)" % (
+            MIXTURE_MAX_K, MIXTURE_MVN_MAX_D, K, D, B))
+    Bl, Kl, Dl = loc.shape
+    Bw, Kw, D1, D2 = W.shape
+    assert Bl in (1, B) and Kl in (1, K) and Dl == D and Bw in (1, B) and Kw in (1, K) and D1 == D2 == D, (
+        tuple(loc.shape), tuple(W.shape), (B, K, D))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    row_lse = torch.empty((B, N), dtype=x.dtype, device=x.device)
+    out = torch.empty((B, J), dtype=torch.float64, device=x.device)
+    check(lib.pa_mixture_mvn_fwd_bwd(_dtype(x), _ptr(x), N, D, K, B, _ptr(a), K, _ptr(loc), D if Kl > 1 else 0,
+                                     Kl * D if Bl > 1 else 0, _ptr(W), D * D if Kw > 1 else 0,
+                                     Kw * D * D if Bw > 1 else 0, _ptr(row_lse), _ptr(ws), ws.numel(), _ptr(out),
+                                     _stream()))
+    S = out[:, 0]
+    R = out[:, 1:1 + K]
+    m = out[:, 1 + K:1 + K + K * D].reshape(B, K, D)
+    G = out[:, 1 + K + K * D:].reshape(B, K, D, D)
+    return S, R, m, G
+
+
 def lda_factor_fwd_bwd(words, log_theta, log_phi, index=None):
     """words int64 [Wd,B]; log_theta [B,T]; log_phi [T,V] -> (out_doc[B], g_theta[B,T], g_phi[T,V]).
     ``index``: an image from lda_build_index (default: the cached one of ``words``, if any)."""

@@ -117,7 +117,25 @@ class LazyFamily:
         return self._packed()
 
 
-FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd
+class LazyMvn(LazyFamily):
+    """log-factor f[k, (b), n] = log MultivariateNormal(x[n] | loc[k, b], scale_tril[k, b]) of an OBSERVED
+    full-covariance site whose parameters were indexed by an enumerated value (``MultivariateNormal(locs[z],
+    scale_tril=L[z])`` under ``plate(n)``), kept un-materialised for csrc/mixture_mvn.hip.  ``loc``: [K | 1, B | 1, D];
+    ``scale_tril``: [K | 1, B | 1, D, D] (from ``covariance_matrix`` / ``precision_matrix`` by torch's own ops)."""
+
+    def __init__(self, value, K, loc, scale_tril, packed, batch_dim=None, B=1):
+        super().__init__(None, value, K, loc, scale_tril, packed, batch_dim, B, value.shape[-1])
+
+    @property
+    def loc(self):
+        return self.p0
+
+    @property
+    def scale_tril(self):
+        return self.p1
+
+
+FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (pa_mixture_mvn_fwd_bwd)
 
 
 @_dispatcher_op("mixture_factor")
@@ -180,6 +198,38 @@ class _MixtureDiagFactor(torch.autograd.Function):
         return None, g1 * da, to_shape(dl, ctx.shapes[0]), to_shape(dc, ctx.shapes[1])
 
 
+@_dispatcher_op("mixture_mvn_factor")
+class _MixtureMvnFactor(torch.autograd.Function):
+    """The mixture leaf for a full-covariance MultivariateNormal (pa_mixture_mvn_fwd_bwd): a [B, K];
+    loc [B | 1, K | 1, D]; W [B | 1, K | 1, D, D] = scale_tril^-1.  The kernel returns R = dS/da and the statistics
+    m, G; the gradients are dS/dloc_k = W_k^T m_k and dS/dW_k = diag(R_k / W_k,ii) - G_k (lower triangle)."""
+
+    @staticmethod
+    def forward(ctx, x, a, loc, W):
+        S, R, m, G = kernels.mixture_mvn_fwd_bwd(x, a, loc, W)
+        ctx.shapes = (tuple(loc.shape), tuple(W.shape))
+        ctx.save_for_backward(R, m, G, W)
+        return S.to(a.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        R, m, G, W = ctx.saved_tensors
+        dt = W.dtype
+        g = g.to(torch.float64)
+        Wd = W.to(torch.float64).expand(G.shape)                     # [B, K, D, D]
+        dloc = g.reshape(-1, 1, 1) * (Wd.transpose(-1, -2) @ m.unsqueeze(-1)).squeeze(-1)
+        dW = torch.diag_embed(R.unsqueeze(-1) / torch.diagonal(Wd, dim1=-2, dim2=-1)) - G
+        dW = g.reshape(-1, 1, 1, 1) * dW
+
+        def to_shape(d, shape):
+            for ax in range(2):
+                if shape[ax] == 1 and d.shape[ax] != 1:
+                    d = d.sum(ax, keepdim=True)
+            return d.to(dt)
+
+        return None, (g.reshape(-1, 1) * R).to(dt), to_shape(dloc, ctx.shapes[0]), to_shape(dW, ctx.shapes[1])
+
+
 def _try_fused_mixture(terms, sum_ids, contract_frames):
     """The mixture leaf: one enumerated name k, ONE lazy observed-family term over (k, [b,] n), every other term a
     function of k (and b) alone -- constant along the data plate --, and the data plate n (dim -1) is contracted
@@ -201,6 +251,8 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
         return None
     x, K, B = lz.value, lz.K, lz.B
     if K > kernels.MIXTURE_MAX_K or K < 1 or B > 65535:
+        return None
+    if isinstance(lz, LazyMvn) and lz.D > kernels.MIXTURE_MVN_MAX_D:
         return None
     nplates = None
     a = None
@@ -230,7 +282,15 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
         q = p.t().contiguous().reshape(-1)             # [Bp, Kp] row-major
         return q, (1 if Kp == K and K > 1 else 0), (Kp if Bp == B and B > 1 else 0)
 
-    if lz.D is not None:                               # a diagonal Normal over features: value [N, D]
+    if isinstance(lz, LazyMvn):                        # a full-covariance MultivariateNormal: value [N, D]
+        D = lz.D
+        # W = L^-1 on [B, K, D, D] by torch (formed in float64: the leaf's accuracy on a badly conditioned L rests on
+        # it); the gradient to L -- and through torch's own ops to covariance_matrix / precision_matrix -- follows
+        L = lz.scale_tril.transpose(0, 1)
+        eye = torch.eye(D, dtype=torch.float64, device=L.device)
+        W = torch.linalg.solve_triangular(L.to(torch.float64), eye, upper=False).to(x.dtype)
+        S = _MixtureMvnFactor.invoke(x.contiguous(), a, lz.loc.transpose(0, 1).contiguous(), W.contiguous())   # [B]
+    elif lz.D is not None:                             # a diagonal Normal over features: value [N, D]
         if lz.p1 is None:
             return None
         S = _MixtureDiagFactor.invoke(x.contiguous(), a, lz.p0.transpose(0, 1).contiguous(),
