@@ -1102,6 +1102,29 @@ int pa_mixture_mvn_fwd_bwd(int dtype, const void* x, int64_t N, int D, int K, in
                            const void* w, int64_t w_stride_k, int64_t w_batch_stride, void* row_lse,
                            void* workspace, size_t workspace_bytes, double* out, pa_stream_t stream);
 
+/* ---- csrc/mixture_event.hip: the mixture leaf for an event-shaped element-wise observation ------------------------
+ * Replaces, for `Fam(p0[z], p1[z]).to_event(1)` observed under the data plate with z enumerated
+ * (pyro/infer/traceenum_elbo.py:112-214, pyro/ops/contract.py:79-160): torch's Independent.log_prob over the
+ * [K, N, D] frame (torch/distributions/independent.py log_prob: the family's element-wise log_prob, then the sum of
+ * the event dim), the logsumexp over K, the plate sum, and the autograd duals of all of them.  Families (`dist`):
+ * PA_DIST_NORMAL, _LOG_NORMAL (p0 = loc, p1 = scale), _EXPONENTIAL (p0 = rate), _BERNOULLI_LOGITS (p0 = logits),
+ * _POISSON (p0 = rate), _GAMMA (p0 = concentration, p1 = rate); p1 NULL for the one-parameter families.
+ *   S[b] = sum_n log sum_k exp(a[b][k] + sum_d lp(x[n][d] | p0[b][k][d], p1[b][k][d])),  K <= 64, 1 <= D <= 1024,
+ * and with r_nk = softmax_k its gradients R[b][k] = dS/da = sum_n r_nk, dS/dp[b][k][d] = sum_n r_nk dlp/dp.
+ * x [N, D] row-major; a[b][k] = a[b * a_batch_stride + k]; p[b][k][d] = p[b * p_batch_stride + k * p_stride_k +
+ * d * p_stride_d] (stride 0: shared).  out[b * J + ...], J = pa_mixture_event_layout(dist, K, D) = 1 + K + K D P
+ * doubles (P = 1 or 2 parameters): [0] = S, [1 + k] = R_k, [1 + K + k D + d] = dS/dp0, [1 + K + K D + k D + d] =
+ * dS/dp1.  row_lse: B N doubles (the rows' logsumexp between the launches).  Workspace:
+ * pa_mixture_event_workspace(dist, K, D, B) bytes, 41.0 MB at K = 64, D = 1024, B = 1 (at most 42 MB at B = 1).
+ * Four launches, no host synchronisation, bit-reproducible.  0 from layout / workspace: outside the limits. */
+int64_t pa_mixture_event_layout(int dist, int K, int D);
+size_t pa_mixture_event_workspace(int dist, int K, int D, int64_t B);
+int pa_mixture_event_fwd_bwd(int dtype, int dist, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                             int64_t a_batch_stride, const void* p0, int64_t p0_stride_k, int64_t p0_stride_d,
+                             int64_t p0_batch_stride, const void* p1, int64_t p1_stride_k, int64_t p1_stride_d,
+                             int64_t p1_batch_stride, void* row_lse, void* workspace, size_t workspace_bytes,
+                             double* out, pa_stream_t stream);
+
 /* ---- csrc/replay.hip: a captured step that is a short chain of kernels, launched as kernels ----------------
  * Replaces nothing of the reference's (its SVI.step, pyro/infer/svi.py:134-162, re-runs the model): it is the
  * replay path of this package's captured step, opt-in on the host side: measured on config 2 a step that waits for

@@ -121,8 +121,9 @@ def _lazy_gather(site, first_enum_dim):
 def _lazy_family(site, first_enum_dim):
     """An observed element-wise site under the data plate (dim -1) -- and at most one outer plate (vectorised
     chains / particles) -- whose parameters were indexed by ONE enumerated value: ``Normal(locs[z], scale)`` with
-    float data [N].  Keep the [K, (B,) N] factor as (family, data, parameters per k and b) for the mixture leaf
-    kernel (ops/contract.py::_try_fused_mixture).  -> (enum id, LazyFamily) or None."""
+    float data [N], or ``Fam(p0[z], p1[z]).to_event(1)`` with data [N, D], D <= 1024, of a family of
+    kernels.MIXTURE_FAMILIES.  Keep the [K, (B,) N] factor as (family, data, parameters per k and b) for the mixture
+    leaf kernel (ops/contract.py::_try_fused_mixture).  -> (enum id, LazyFamily) or None."""
     from ..ops import contract
     fn, value = site["fn"], site["value"]
     if not contract.FUSED_MIXTURE or not site["is_observed"] or not (site["mask"] is None or site["mask"] is True):
@@ -134,9 +135,9 @@ def _lazy_family(site, first_enum_dim):
     if not isinstance(value, torch.Tensor) or value.dim() != 1 + len(ev) or value.requires_grad \
             or value.dtype not in (torch.float32, torch.float64) or not kernels.on_device(value):
         return None
-    if len(ev) > 1 or (len(ev) == 1 and (ev[0] > kernels.MIXTURE_MAX_D or value.shape[1] != ev[0])):
+    if len(ev) > 1 or (len(ev) == 1 and (ev[0] > kernels.MIXTURE_EVENT_MAX_D or value.shape[1] != ev[0])):
         return None
-    D = ev[0] if ev else None                 # a diagonal family over D features (to_event(1)) or scalar data
+    D = ev[0] if ev else None                 # an element-wise family over D features (to_event(1)) or scalar data
     plate_dims = sorted(f.dim for f in site["cond_indep_stack"] if f.vectorized)
     if not plate_dims or plate_dims[-1] != -1 or len(plate_dims) > 2:
         return None
@@ -161,8 +162,8 @@ def _lazy_family(site, first_enum_dim):
     ent = entry(value, 1.0, None)
     if ent is None or ent[0] not in kernels.MIXTURE_FAMILIES or K > kernels.MIXTURE_MAX_K:
         return None
-    if D is not None and ent[0] != kernels._lib.DIST_NORMAL:
-        return None                           # (the event-shaped leaf scores the diagonal Normal only)
+    # (the event leaf takes each parameter at its own size: torch's two-parameter families broadcast them)
+    event_leaf = D is not None and not (ent[0] == kernels._lib.DIST_NORMAL and D <= kernels.MIXTURE_MAX_D)
     params = []
     for p in (ent[2], ent[3]):
         if p is None:
@@ -170,6 +171,8 @@ def _lazy_family(site, first_enum_dim):
             continue
         if not isinstance(p, torch.Tensor) or p.dtype != value.dtype or not kernels.on_device(p):
             return None
+        if event_leaf:
+            p = _unexpanded(p)
         ne = 0 if D is None else 1            # trailing event dims of the parameter
         if p.dim() > nb + ne:
             return None
@@ -195,8 +198,6 @@ def _lazy_family(site, first_enum_dim):
         lp = fn.log_prob(value, *site["args"], **site["kwargs"])
         return _packed(site, lp, first_enum_dim).tensor
 
-    if D is not None and params[1] is None:
-        return None
     return site["infer"]["_dim_to_id"][edim], contract.LazyFamily(ent[0], value, K, params[0], params[1], packed,
                                                                   batch_dim, B, D)
 

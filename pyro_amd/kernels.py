@@ -2052,6 +2052,53 @@ def mixture_mvn_fwd_bwd(x, a, loc, W):
     return S, R, m, G
 
 
+MIXTURE_EVENT_MAX_D = 1024
+
+
+def mixture_event_fwd_bwd(dist_id, x, a, p0, p1):
+    """The mixture leaf for an event-shaped observation ``Fam(p0[z], p1[z]).to_event(1)`` over D <= 1024 features
+    (pa_mixture_event_fwd_bwd), for every family of MIXTURE_FAMILIES: x [N, D]; a [B, K]; p0, p1 [B | 1, K | 1, D | 1]
+    (contiguous, of x's dtype; p1 None for the one-parameter families).  -> (S [B], dS/da [B, K], dS/dp0 [B, K, D],
+    dS/dp1 [B, K, D] or None) in float64 on the device, per (b, k, d): a shared parameter takes the sum."""
+    _require_gpu(x, a, p0, p1)
+    N, D = x.shape
+    B, K = a.shape
+    assert x.is_contiguous() and a.is_contiguous() and p0.is_contiguous() and (p1 is None or p1.is_contiguous())
+    assert p0.dim() == 3 and (p1 is None or p1.dim() == 3)
+    assert a.dtype == x.dtype == p0.dtype and (p1 is None or p1.dtype == x.dtype)
+    lib = _lib.load()
+    J = lib.pa_mixture_event_layout(int(dist_id), K, D)
+    nbytes = lib.pa_mixture_event_workspace(int(dist_id), K, D, B)
+    if J == 0 or nbytes == 0 or N < 1:
+        raise Unsupported("pyro_amd: mixture_event_fwd_bwd needs a family of MIXTURE_FAMILIES, 1 <= K <= %d, "
+                          "1 <= D <= %d, 1 <= B <= 65535, N >= 1 (dist=%d, K=%d, D=%d, B=%d, N=%d)" % (
+                              MIXTURE_MAX_K, MIXTURE_EVENT_MAX_D, int(dist_id), K, D, B, N))
+    npar = (J - 1 - K) // (K * D)
+    if (p1 is None) != (npar == 1):
+        raise Unsupported("pyro_amd: mixture_event_fwd_bwd: family %d takes %d parameter(s)" % (int(dist_id), npar))
+
+    def strides(p):
+        if p is None:
+            return 0, 0, 0
+        Bp, Kp, Dp = p.shape
+        assert Bp in (1, B) and Kp in (1, K) and Dp in (1, D), (tuple(p.shape), (B, K, D))
+        return (Dp if Kp > 1 else 0), (1 if Dp > 1 else 0), (Kp * Dp if Bp > 1 else 0)
+
+    k0, d0, b0 = strides(p0)
+    k1, d1, b1 = strides(p1)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    row_lse = torch.empty((B, N), dtype=torch.float64, device=x.device)
+    out = torch.empty((B, J), dtype=torch.float64, device=x.device)
+    check(lib.pa_mixture_event_fwd_bwd(_dtype(x), int(dist_id), _ptr(x), N, D, K, B, _ptr(a), K, _ptr(p0), k0, d0,
+                                       b0, _ptr(p1) if p1 is not None else None, k1, d1, b1, _ptr(row_lse), _ptr(ws),
+                                       ws.numel(), _ptr(out), _stream()))
+    S = out[:, 0]
+    da = out[:, 1:1 + K]
+    g0 = out[:, 1 + K:1 + K + K * D].reshape(B, K, D)
+    g1 = out[:, 1 + K + K * D:].reshape(B, K, D) if npar == 2 else None
+    return S, da, g0, g1
+
+
 def lda_factor_fwd_bwd(words, log_theta, log_phi, index=None):
     """words int64 [Wd,B]; log_theta [B,T]; log_phi [T,V] -> (out_doc[B], g_theta[B,T], g_phi[T,V]).
     ``index``: an image from lda_build_index (default: the cached one of ``words``, if any)."""

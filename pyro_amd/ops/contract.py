@@ -109,8 +109,8 @@ class LazyFamily:
     def __init__(self, dist_id, value, K, p0, p1, packed, batch_dim=None, B=1, D=None):
         self.dist_id, self.value, self.K, self.p0, self.p1, self._packed = dist_id, value, K, p0, p1, packed
         self.batch_dim, self.B = batch_dim, B
-        # D: the event size of a diagonal Normal over features (value [N, D], p0 / p1 [K | 1, B | 1, D | 1]); None:
-        # scalar observations (p0 / p1 [K | 1, B | 1])
+        # D: the event size of an element-wise family over features (value [N, D], p0 / p1 [K | 1, B | 1, D | 1],
+        # p1 None for one-parameter families); None: scalar observations (p0 / p1 [K | 1, B | 1])
         self.D = D
 
     def materialize(self):
@@ -135,7 +135,7 @@ class LazyMvn(LazyFamily):
         return self.p1
 
 
-FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (pa_mixture_mvn_fwd_bwd)
+FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (_diag_normal, _event, _mvn)
 
 
 @_dispatcher_op("mixture_factor")
@@ -230,6 +230,36 @@ class _MixtureMvnFactor(torch.autograd.Function):
         return None, (g.reshape(-1, 1) * R).to(dt), to_shape(dloc, ctx.shapes[0]), to_shape(dW, ctx.shapes[1])
 
 
+@_dispatcher_op("mixture_event_factor")
+class _MixtureEventFactor(torch.autograd.Function):
+    """The mixture leaf for an event-shaped observation ``Fam(p0[z], p1[z]).to_event(1)`` over D <= 1024 features
+    (pa_mixture_event_fwd_bwd): a [B, K]; p0 / p1 [B | 1, K | 1, D | 1] (p1 None for one-parameter families)."""
+
+    @staticmethod
+    def forward(ctx, dist_id, x, a, p0, p1):
+        S, da, d0, d1 = kernels.mixture_event_fwd_bwd(dist_id, x, a, p0, p1)
+        dt = a.dtype
+        ctx.shapes = (tuple(p0.shape), None if p1 is None else tuple(p1.shape))
+        ctx.save_for_backward(da.to(dt), d0.to(dt), None if d1 is None else d1.to(dt))
+        return S.to(dt)
+
+    @staticmethod
+    def backward(ctx, g):
+        da, d0, d1 = ctx.saved_tensors
+        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
+
+        def to_shape(d, shape):
+            if d is None:
+                return None
+            d = g2 * d                                  # [B, K, D]
+            for ax in range(3):
+                if shape[ax] == 1 and d.shape[ax] != 1:
+                    d = d.sum(ax, keepdim=True)
+            return d
+
+        return None, None, g1 * da, to_shape(d0, ctx.shapes[0]), to_shape(d1, ctx.shapes[1])
+
+
 def _try_fused_mixture(terms, sum_ids, contract_frames):
     """The mixture leaf: one enumerated name k, ONE lazy observed-family term over (k, [b,] n), every other term a
     function of k (and b) alone -- constant along the data plate --, and the data plate n (dim -1) is contracted
@@ -290,11 +320,16 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
         eye = torch.eye(D, dtype=torch.float64, device=L.device)
         W = torch.linalg.solve_triangular(L.to(torch.float64), eye, upper=False).to(x.dtype)
         S = _MixtureMvnFactor.invoke(x.contiguous(), a, lz.loc.transpose(0, 1).contiguous(), W.contiguous())   # [B]
-    elif lz.D is not None:                             # a diagonal Normal over features: value [N, D]
-        if lz.p1 is None:
-            return None
+    elif lz.D is not None and lz.dist_id == kernels._lib.DIST_NORMAL and lz.D <= kernels.MIXTURE_MAX_D:
+        # a diagonal Normal over at most 8 features: value [N, D]
         S = _MixtureDiagFactor.invoke(x.contiguous(), a, lz.p0.transpose(0, 1).contiguous(),
                                       lz.p1.transpose(0, 1).contiguous())                          # [B]
+    elif lz.D is not None:                             # any other element-wise family over features: value [N, D]
+        if lz.D > kernels.MIXTURE_EVENT_MAX_D:
+            return None
+        p1 = None if lz.p1 is None else lz.p1.transpose(0, 1).contiguous()
+        S = _MixtureEventFactor.invoke(int(lz.dist_id), x.contiguous(), a, lz.p0.transpose(0, 1).contiguous(),
+                                       p1)                                                         # [B]
     else:
         p0, s0, bs0 = flat(lz.p0)
         p1, s1, bs1 = flat(lz.p1)
