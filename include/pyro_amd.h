@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 8
+#define PA_ABI_VERSION 9
 
 enum { PA_OK = 0, PA_ERR_INVALID = -1, PA_ERR_UNSUPPORTED = -2, PA_ERR_LAUNCH = -3 };
 
@@ -954,6 +954,19 @@ int pa_tall_linear_act(const float* G, int64_t B, int64_t R, const float* W, int
                        int sigmoid_out, float* Y, pa_stream_t stream);
 int pa_tall_wgrad_act(const float* G, const float* X, const float* y_mul, int64_t B, int64_t R, int64_t K,
                       float* dW, float* db, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+/* Which kernel the two launchers above would run for these arguments (ABI 9): pure host functions that launch
+ * nothing and that the launchers themselves call, so that a test can tell which path it exercised.
+ *   pa_tall_linear_path: NKS | NCT << 4 | NW << 8 | stage << 16 | wvec << 17 -- the (NKS, NCT) instantiation
+ *     ((1,4), (8,1), (7,4), (8,4)), 4 or 16 waves per workgroup, the weight staged through LDS, and, unstaged,
+ *     16-byte vector reads (1) or 8-way gathers (0) of the weight.  *_aligned16: the pointer is 16-byte aligned
+ *     (ymul_aligned16 = 1 without a y_mul).
+ *   pa_tall_wgrad_path:  NCT | NW << 4 | nrt << 8 | JW << 12 -- column tiles of X, 4 or 8 waves per workgroup,
+ *     row tiles per workgroup (1, 2, 4; three tiles run as 4), outputs per workgroup of the reduce (16 or 64).
+ * Both depend on the device's CU count and on PA_TALL_WAVES (4 | 16, read once per process: pins the wave
+ * count where the operands allow it).  -1: shape not covered. */
+int pa_tall_linear_path(int64_t B, int64_t R, int64_t C, int64_t w_row_stride, int64_t w_col_stride,
+                        int g_aligned16, int ymul_aligned16, int w_aligned16);
+int pa_tall_wgrad_path(int64_t B, int64_t R, int64_t K);
 
 /* Reparameterised standard-Gamma draws out[i] ~ Gamma(alpha[i], 1) on the keyed Philox stream and,
  * when d_alpha != NULL, the implicit reparameterisation gradient d out[i] / d alpha[i].  Replaces

@@ -63,9 +63,14 @@ __device__ __forceinline__ float bf16_hi(uint32_t p) {
   return __builtin_bit_cast(float, p & 0xffff0000u);
 }
 
-// (a, b) -> three packed bf16 pairs with a = a1+a2+a3, b = b1+b2+b3 (exact for finite inputs whose
-// leading piece does not overflow bf16).  Written on 2-vectors so that the residuals are one
-// v_pk_add_f32 each.
+// (a, b) -> three packed bf16 pairs with a = a1+a2+a3, b = b1+b2+b3.  Exact for binary exponents -110 .. 126
+// (and up to 0x7f7f7fff = 3.39615e38): measured on gfx950 by tests/test_layer_edges_gpu.py::test_split_domain and
+// the same range as torch's round-to-nearest conversion on the CPU (tests/test_layer_edges_host.py) --
+// v_cvt_pk_bf16_f32 and the bf16 MFMA keep bf16 denormals.  Below 2^-110 the third piece falls under bf16's
+// smallest denormal (2^-133): 40-200 u of error at 2^-118, the piece lost whole at 2^-126.  From 0x7f7f8000
+// (3.39618e38) on the leading piece rounds to inf, the second is -inf and the third NaN; an infinite input gives
+// (inf, NaN, NaN): a non-finite operand element makes its output row / column NaN, never a finite value.
+// Written on 2-vectors so that the residuals are one v_pk_add_f32 each.
 __device__ __forceinline__ void split_pair(float a, float b, uint32_t& p1, uint32_t& p2,
                                            uint32_t& p3) {
   const f32x2v v = {a, b};

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64 * NW) void tall_linear_kernel(const float* __res
                                                           int64_t w_cs, int C,
                                                           const float* __restrict__ bias,
                                                           const float* __restrict__ Ymul, int act,
-                                                          float* __restrict__ Y, int stage) {
+                                                          float* __restrict__ Y, int stage, int wvec) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tall_smem[];
   uint4* wsm = reinterpret_cast<uint4*>(tall_smem);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * NW) void tall_linear_kernel(const float* __res
     float wv[NBLK][8];
     // (the forward's Wm = weight^T: a lane's 8 values are consecutive in memory -- two 16-byte loads instead of
     //  eight gathers that touch 64 cache lines each: 224 of those per workgroup were ~7 us of the CU's texture path)
-    const bool wvec = w_rs == 1 && (w_cs & 3) == 0 && (R & 3) == 0 && ((uintptr_t)W & 15) == 0;
+    // (wvec: the launcher's plan -- w_rs == 1, w_cs % 4 == 0, R % 4 == 0 and a 16-byte aligned W)
 #pragma unroll
     for (int i = 0; i < NBLK; ++i) {
       const int blk = wave + NW * i;
@@ -485,6 +485,60 @@ static int tall_wgrad_grid(int64_t B, int nw) {
   return (int)(g < 1 ? 1 : g);
 }
 
+// Which tall_linear_kernel runs and how it reads its operands: the ONE place this is decided (the launcher and
+// pa_tall_linear_path both ask here).
+struct TallLinearPlan {
+  int nks, nct;      // the instantiation's k-steps / column tiles: (1, 4), (8, 1), (7, 4), (8, 4); 0 = none
+  int nw;            // waves per workgroup: 4 or 16
+  int stage;         // the weight travels once into LDS in memory order (sixteen-wave form only)
+  int wvec;          // unstaged: a lane's 8 weights are two 16-byte loads (otherwise eight gathers)
+};
+
+static TallLinearPlan tall_linear_plan(int64_t B, int64_t R, int64_t C, int64_t w_rs, int64_t w_cs,
+                                       bool g_al16, bool y_al16, bool w_al16) {
+  TallLinearPlan p = {0, 0, 4, 0, 0};
+  const int nks = (int)((R + 15) / 16), nct = (int)((C + 31) / 32);
+  if (nks <= 1 && nct <= 4) { p.nks = 1; p.nct = 4; }
+  else if (nks <= 8 && nct <= 1) { p.nks = 8; p.nct = 1; }
+  else if (nks <= 7 && nct <= 4) { p.nks = 7; p.nct = 4; }
+  else if (nks <= 8 && nct <= 4) { p.nks = 8; p.nct = 4; }
+  else return p;
+  const int64_t ntiles = (B + 31) / 32;
+  // sixteen waves per workgroup (four per SIMD, one tile each) once there is a tile for every wave of a
+  // quarter of the chip; below that the four-wave form (fewer, longer-lived waves: the planes' prologue is
+  // per workgroup)
+  p.nw = tall_waves() != 0 ? tall_waves() : (ntiles >= (int64_t)cu_count() * 4 ? 16 : 4);
+  // (the sixteen-wave form reads rows in 16-byte granules through 32-bit buffer offsets)
+  if ((R & 3) != 0 || B * R >= (1ll << 29) || !g_al16 || !y_al16) p.nw = 4;
+  // a contiguous weight is staged through LDS in memory order (sixteen-wave form, when it fits behind the planes)
+  const bool contiguous = (w_rs == 1 && w_cs == R) || (w_cs == 1 && w_rs == C);
+  const size_t stage_bytes = ((size_t)R * C * 4 + 15) & ~(size_t)15;
+  p.stage = p.nw == 16 && contiguous && ((R * C) & 3) == 0 && w_al16 &&
+            (size_t)p.nks * p.nct * 3 * 1024 + stage_bytes <= (size_t)156 * 1024;
+  p.wvec = !p.stage && w_rs == 1 && (w_cs & 3) == 0 && (R & 3) == 0 && w_al16;
+  return p;
+}
+
+struct TallWgradPlan {
+  int nct;           // column tiles of X: ceil(K / 32)
+  int nw;            // waves per workgroup: 4, or 8 (pairs of waves added through LDS)
+  int nrt;           // row tiles a workgroup's waves cycle through: 1, 2 or 4 (3 is run as 4)
+  int jw;            // outputs per workgroup of the reduce kernel: 64 or 16
+};
+
+static TallWgradPlan tall_wgrad_plan(int64_t B, int64_t R, int64_t K) {
+  TallWgradPlan p;
+  p.nrt = (int)((R + 31) / 32);
+  if (p.nrt == 3) p.nrt = 4;                           // (a wave's tile index is gw % nrt, 4 waves per workgroup)
+  // eight waves per workgroup (two per SIMD) once every wave has k-steps for its three register sets
+  const int64_t nks16 = (B + 15) / 16;
+  const int tw = tall_waves();
+  p.nw = tw == 4 ? 4 : tw == 16 ? 8 : (nks16 * p.nrt >= (int64_t)cu_count() * 8 * 3 ? 8 : 4);
+  p.nct = (int)((K + 31) / 32);
+  p.jw = R * K + R >= 4096 ? 64 : 16;
+  return p;
+}
+
 }  // namespace pa
 
 extern "C" {
@@ -502,35 +556,29 @@ int pa_tall_linear_act(const float* G, int64_t B, int64_t R, const float* W, int
              (long long)C);
   if (B == 0) return PA_OK;
   PA_REQUIRE(G && W && Y, "tall_linear: NULL pointer");
+  const pa::TallLinearPlan pl = pa::tall_linear_plan(B, R, C, w_row_stride, w_col_stride, ((uintptr_t)G & 15) == 0,
+                                                     y_mul == nullptr || ((uintptr_t)y_mul & 15) == 0,
+                                                     ((uintptr_t)W & 15) == 0);
   const int nks = (int)((R + 15) / 16), nct = (int)((C + 31) / 32);
   const int64_t ntiles = (B + 31) / 32;
-  // sixteen waves per workgroup (four per SIMD, one tile each) once there is a tile for every wave of a
-  // quarter of the chip; below that the four-wave form (fewer, longer-lived waves: the planes' prologue is
-  // per workgroup)
-  int nw = pa::tall_waves() != 0 ? pa::tall_waves() : (ntiles >= (int64_t)pa::cu_count() * 4 ? 16 : 4);
-  // (the sixteen-wave form reads rows in 16-byte granules through 32-bit buffer offsets)
-  if ((R & 3) != 0 || B * R >= (1ll << 29) || ((uintptr_t)G & 15) != 0 || (y_mul && ((uintptr_t)y_mul & 15) != 0)) nw = 4;
+  const int nw = pl.nw;
   int64_t grid = (ntiles + nw - 1) / nw;
   const int64_t cap = (int64_t)pa::cu_count() * (nw == 16 || nks * nct > 16 ? 1 : 2);
   if (grid > cap) grid = cap;
-  // a contiguous weight is staged through LDS in memory order (sixteen-wave form, when it fits behind the planes)
-  const bool contiguous = (w_row_stride == 1 && w_col_stride == R) || (w_col_stride == 1 && w_row_stride == C);
   const size_t stage_bytes = ((size_t)R * C * 4 + 15) & ~(size_t)15;
   hipStream_t s = pa::as_stream(stream);
 #define PA_TALL_LAUNCH(NKS_, NCT_, NW_)                                                                \
   {                                                                                                    \
     auto k = pa::tall_linear_kernel<NKS_, NCT_, NW_>;                                                  \
     size_t l = (size_t)NKS_ * NCT_ * 3 * 1024;                                                         \
-    const int stage = NW_ == 16 && contiguous && ((R * C) & 3) == 0 && ((uintptr_t)W & 15) == 0 &&     \
-                      l + stage_bytes <= (size_t)156 * 1024;                                           \
-    if (stage) l += stage_bytes;                                                                       \
+    if (pl.stage) l += stage_bytes;                                                                    \
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l);     \
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * NW_), l, s, G, B, (int)R, W, w_row_stride,   \
-                       w_col_stride, (int)C, bias, y_mul, sigmoid_out, Y, stage);                      \
+                       w_col_stride, (int)C, bias, y_mul, sigmoid_out, Y, pl.stage, pl.wvec);          \
     return pa::check_launch("tall_linear_kernel");                                                     \
   }
 #define PA_TALL_CASE(NKS_, NCT_)                                                                       \
-  if (nks <= NKS_ && nct <= NCT_) {                                                                    \
+  if (pl.nks == NKS_ && pl.nct == NCT_) {                                                              \
     if (nw == 16) PA_TALL_LAUNCH(NKS_, NCT_, 16)                                                       \
     PA_TALL_LAUNCH(NKS_, NCT_, 4)                                                                      \
   }
@@ -541,6 +589,21 @@ int pa_tall_linear_act(const float* G, int64_t B, int64_t R, const float* W, int
 #undef PA_TALL_CASE
 #undef PA_TALL_LAUNCH
   return pa::fail(PA_ERR_UNSUPPORTED, "tall_linear: no kernel for R=%lld C=%lld", (long long)R, (long long)C);
+}
+
+int pa_tall_linear_path(int64_t B, int64_t R, int64_t C, int64_t w_row_stride, int64_t w_col_stride,
+                        int g_aligned16, int ymul_aligned16, int w_aligned16) {
+  if (B < 0 || R < 1 || R > pa::TALL_MAX || C < 1 || C > pa::TALL_MAX) return -1;
+  const pa::TallLinearPlan p = pa::tall_linear_plan(B, R, C, w_row_stride, w_col_stride, g_aligned16 != 0,
+                                                    ymul_aligned16 != 0, w_aligned16 != 0);
+  if (p.nks == 0) return -1;
+  return p.nks | (p.nct << 4) | (p.nw << 8) | (p.stage << 16) | (p.wvec << 17);
+}
+
+int pa_tall_wgrad_path(int64_t B, int64_t R, int64_t K) {
+  if (B < 0 || R < 1 || R > pa::TALL_MAX || K < 1 || K > pa::TALL_MAX) return -1;
+  const pa::TallWgradPlan p = pa::tall_wgrad_plan(B, R, K);
+  return p.nct | (p.nw << 4) | (p.nrt << 8) | (p.jw << 12);
 }
 
 size_t pa_tall_wgrad_workspace(int64_t B, int64_t R, int64_t K) {
@@ -569,17 +632,13 @@ int pa_tall_wgrad_act(const float* G, const float* X, const float* y_mul, int64_
   }
   PA_REQUIRE(G && X && workspace, "tall_wgrad: NULL pointer");
   PA_REQUIRE(workspace_bytes >= pa_tall_wgrad_workspace(B, R, K), "tall_wgrad: workspace too small");
-  int nrt = (int)((R + 31) / 32);
-  if (nrt == 3) nrt = 4;                               // (a wave's tile index is gw % nrt, 4 waves per workgroup)
-  // eight waves per workgroup (two per SIMD) once every wave has k-steps for its three register sets
-  const int64_t nks16 = (B + 15) / 16;
-  const int tw = pa::tall_waves();
-  const int nw = tw == 4 ? 4 : tw == 16 ? 8 : (nks16 * nrt >= (int64_t)pa::cu_count() * 8 * 3 ? 8 : 4);
+  const pa::TallWgradPlan pl = pa::tall_wgrad_plan(B, R, K);
+  const int nrt = pl.nrt, nw = pl.nw;
   const int grid = pa::tall_wgrad_grid(B, nw);
   const int64_t nwaves = (int64_t)grid * 4;            // partial tiles (the eight-wave form adds pairs in LDS)
   float* part = (float*)workspace;
   float* part_db = part + nwaves * (32 * pa::TALL_MAX);
-  const int nct = (int)((K + 31) / 32);
+  const int nct = pl.nct;
 #define PA_TALLW_CASE(NCT_)                                                                            \
   if (nct == NCT_) {                                                                                   \
     if (nw == 8) {                                                                                     \
@@ -599,7 +658,7 @@ int pa_tall_wgrad_act(const float* G, const float* X, const float* y_mul, int64_
   PA_TALLW_CASE(4)
 #undef PA_TALLW_CASE
   const int64_t n = R * K + R;
-  if (n >= 4096)
+  if (pl.jw == 64)
     hipLaunchKernelGGL(pa::tall_wgrad_reduce_kernel<64>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, part,
                        part_db, nwaves, nrt, (int)R, (int)K, dW, db);
   else

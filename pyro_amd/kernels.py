@@ -2252,6 +2252,28 @@ def tall_linear(g, W, w_row_stride, w_col_stride, C, bias=None, y_mul=None, sigm
     return out
 
 
+def _aligned16(t):
+    return int(t is None or t.data_ptr() % 16 == 0)
+
+
+def tall_linear_path(B, R, C, w_row_stride, w_col_stride, g=None, y_mul=None, W=None):
+    """Which kernel pa_tall_linear_act runs for these arguments (pa_tall_linear_path; the tensors only give
+    their alignment, None = aligned): dict(nks, nct, nw, stage, wvec).  Launches nothing."""
+    v = _lib.load().pa_tall_linear_path(int(B), int(R), int(C), int(w_row_stride), int(w_col_stride),
+                                        _aligned16(g), _aligned16(y_mul), _aligned16(W))
+    if v < 0:
+        raise Unsupported("pyro_amd: tall_linear covers at most 128 features (R=%d C=%d)" % (R, C))
+    return {"nks": v & 15, "nct": (v >> 4) & 15, "nw": (v >> 8) & 255, "stage": (v >> 16) & 1, "wvec": (v >> 17) & 1}
+
+
+def tall_wgrad_path(B, R, K):
+    """Which kernels pa_tall_wgrad_act runs (pa_tall_wgrad_path): dict(nct, nw, nrt, jw).  Launches nothing."""
+    v = _lib.load().pa_tall_wgrad_path(int(B), int(R), int(K))
+    if v < 0:
+        raise Unsupported("pyro_amd: tall_wgrad covers at most 128 features (R=%d K=%d)" % (R, K))
+    return {"nct": v & 15, "nw": (v >> 4) & 15, "nrt": (v >> 8) & 15, "jw": (v >> 12) & 255}
+
+
 def tall_wgrad(g, x, want_bias=True, y_mul=None):
     """(d[B, R].T @ x[B, K], d.sum(0)) in one pass over the batch with d = g, or g * (1 - y_mul) * y_mul:
     pa_tall_wgrad_act."""

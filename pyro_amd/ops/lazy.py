@@ -499,7 +499,12 @@ class DeferredLinear:
     kernel's epilogue, and its backward takes the gradient THROUGH the sigmoid in the operand loads of dx /
     dW / db (pa_tall_linear_act, pa_tall_wgrad_act, pa_bow_linear_*_act) -- torch's two extra passes over
     [B, features] in each direction are gone.  ANY other use launches the plain layer and goes on with its
-    result (a TallActivation), exactly as before."""
+    result (a TallActivation), exactly as before.
+
+    Any f32 tensor goes to these kernels (non-contiguous ones through .contiguous(), any storage offset).  Their
+    three-piece bf16 operand split is exact for magnitudes 2^-110 .. 3.396e38 (csrc/glm_bf16.h); an element of
+    magnitude >= 3.39618e38 (finite in f32) makes its output row NaN where torch's f32 product is finite, as an
+    inf or a NaN does, and elements below 2^-110 lose their last bits (f32-class no longer)."""
 
     def __init__(self, kind, args, shape, like):
         self.kind, self.args = kind, args
