@@ -1138,6 +1138,45 @@ int pa_mixture_event_fwd_bwd(int dtype, int dist, const void* x, int64_t N, int 
                              int64_t p1_batch_stride, void* row_lse, void* workspace, size_t workspace_bytes,
                              double* out, pa_stream_t stream);
 
+/* ---- csrc/mixture_rows.hip: the leaves of csrc/mixture.hip with per-row assignment weights -----------------------
+ * Replaces, for a plated mixture whose enumerated Categorical has probabilities that differ from row to row (a gating
+ * network, grouped weights, soft or one-hot labels) under TraceEnum_ELBO (pyro/infer/traceenum_elbo.py:112-214): the
+ * two [K, N] log-factors (pyro/poutine/trace_struct.py:248-288), their add and the logsumexp over the enumerated
+ * variable (pyro/ops/contract.py:79-160, pyro/ops/einsum/torch_log.py:14-55), the plate sum, and the autograd duals.
+ *   S[b] = sum_n log sum_k exp(a[b][n][k] + log p(x[n] | p0[b][k], p1[b][k]))     (K <= 64, 1 <= B <= 65535),
+ * a[b][n][k] = a[b * a_batch_stride + n * a_stride_n + k * a_stride_k] (non-negative element strides; batch stride
+ * 0: weights shared by the sets; a_stride_k = 1 is the coalesced layout, and the only one besides 0 that the Python
+ * package passes and the tests run: it copies any other layout to row-major first); x, p0, p1, families and dtypes as
+ * pa_mixture_fwd_bwd.  da: B N K values of `dtype`, row-major -- da[(b N + n) K + k] = dS/da[b][n][k], the
+ * responsibilities, written once -- or NULL: the weights need no gradient and nothing of size K N is written.
+ * out_padded[b * J + ...], J = pa_mixture_rows_layout(K, &KP) = 1 + 2 KP doubles: [0] = S, [1 + k] = dS/dp0_k,
+ * [1 + KP + k] = dS/dp1_k (per (b, k): a shared parameter takes their sum; entries past K are zero).  An entry
+ * a = -inf has responsibility 0; a row whose every term is -inf contributes -inf to S and no responsibilities; NaN
+ * propagates.  Workspace: pa_mixture_rows_workspace(K, B) bytes.  Outside the limits: PA_ERR_UNSUPPORTED (0 from
+ * layout / workspace) before any launch.  Two launches, no host synchronisation, bit-reproducible. */
+int pa_mixture_rows_layout(int K, int* kp_out);
+size_t pa_mixture_rows_workspace(int K, int64_t B);
+int pa_mixture_rows_fwd_bwd(int dtype, int dist, const void* x, int64_t N, int K, int64_t B, const void* a,
+                            int64_t a_stride_k, int64_t a_stride_n, int64_t a_batch_stride, const void* p0,
+                            int64_t p0_stride, int64_t p0_batch_stride, const void* p1, int64_t p1_stride,
+                            int64_t p1_batch_stride, void* da, void* workspace, size_t workspace_bytes,
+                            double* out_padded, pa_stream_t stream);
+
+/* The same for a diagonal Normal over D <= 8 features inside the logsumexp (pa_mixture_diag_normal_fwd_bwd with
+ * per-row weights; torch/distributions/independent.py:96-98 for the sum over the features): x [N, D] row-major, loc
+ * and scale addressed as there, a and da as above.  out_padded[b * J + ...], J =
+ * pa_mixture_rows_diag_normal_layout(K, D, &KP, &DD) = 1 + 2 KP DD doubles: [0] = S, [1 + k * DD + d] = dS/dloc_kd,
+ * [1 + KP * DD + k * DD + d] = dS/dscale_kd.  Workspace: pa_mixture_rows_diag_normal_workspace(K, D, B) bytes. */
+int pa_mixture_rows_diag_normal_layout(int K, int D, int* kp_out, int* dd_out);
+size_t pa_mixture_rows_diag_normal_workspace(int K, int D, int64_t B);
+int pa_mixture_rows_diag_normal_fwd_bwd(int dtype, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                                        int64_t a_stride_k, int64_t a_stride_n, int64_t a_batch_stride,
+                                        const void* loc, int64_t loc_stride_k, int64_t loc_stride_d,
+                                        int64_t loc_batch_stride, const void* scale, int64_t scale_stride_k,
+                                        int64_t scale_stride_d, int64_t scale_batch_stride, void* da,
+                                        void* workspace, size_t workspace_bytes, double* out_padded,
+                                        pa_stream_t stream);
+
 /* ---- csrc/replay.hip: a captured step that is a short chain of kernels, launched as kernels ----------------
  * Replaces nothing of the reference's (its SVI.step, pyro/infer/svi.py:134-162, re-runs the model): it is the
  * replay path of this package's captured step, opt-in on the host side: measured on config 2 a step that waits for

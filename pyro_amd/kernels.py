@@ -2014,6 +2014,89 @@ def mixture_diag_normal_fwd_bwd(x, a, loc, scale):
     return S, da, dl, dc
 
 
+def _row_weights(a, N):
+    """a [B, N, K] (any view) -> (tensor to address, stride_k, stride_n, batch_stride).  The kernels read any
+    non-negative strides; the coalesced layout is component stride 1 (row-major [N, K] memory: the transposed view
+    an enumerated Categorical's own log_prob is), passed as it is, a set-stride of 0 (weights shared by the sets)
+    included.  Every other layout -- a [K, N]-contiguous term out of a gather, say -- pays ONE row-major copy here
+    (of one set when the sets share the weights) instead of K-strided reads."""
+    B, Na, K = a.shape
+    assert Na == N, (tuple(a.shape), N)
+    sb, sn, sk = a.stride()
+    if K > 1 and sk != 1:
+        shared = B > 1 and sb == 0
+        a = (a[:1] if shared else a).contiguous()
+        sb, sn, sk = (0 if shared else N * K), K, 1
+    return a, (sk if K > 1 else 0), (sn if N > 1 else 0), (sb if B > 1 else 0)
+
+
+def mixture_rows_fwd_bwd(dist_id, x, a, p0, s0, p1, s1, p0_bs=0, p1_bs=0, want_da=True):
+    """The mixture leaf with per-row assignment weights (pa_mixture_rows_fwd_bwd): S[b] = sum_n logsumexp_k(a[b, n, k]
+    + log p(x[n] | p0[b, k], p1[b, k])) and its gradients from ONE pass over x and a.  x [N]; a [B, N, K] or a view of
+    that shape (see _row_weights for the layouts that pay a copy); p0 / p1 flat, addressed b * bs + k * s as for
+    mixture_fwd_bwd.  -> (S [B], dS/da [B, N, K] in a's dtype -- the responsibilities -- or None when ``want_da`` is
+    false (nothing of size K N is written then), dS/dp0 [B, K], dS/dp1 [B, K] or None), the sums in float64."""
+    _require_gpu(x, a, p0, p1)
+    N = x.numel()
+    assert a.dim() == 3 and x.is_contiguous() and p0.is_contiguous() and (p1 is None or p1.is_contiguous())
+    assert a.dtype == x.dtype and p0.dtype == x.dtype and (p1 is None or p1.dtype == x.dtype)
+    B, _, K = a.shape
+    lib = _lib.load()
+    kp = ctypes.c_int()
+    J = lib.pa_mixture_rows_layout(K, ctypes.byref(kp))
+    nbytes = lib.pa_mixture_rows_workspace(K, B)
+    if J == 0 or nbytes == 0 or int(dist_id) not in MIXTURE_FAMILIES:
+        raise Unsupported("pyro_amd: mixture_rows_fwd_bwd needs a family of MIXTURE_FAMILIES, 1 <= K <= %d, "
+                          "1 <= B <= 65535 (family %d, K=%d, B=%d)" % (MIXTURE_MAX_K, int(dist_id), K, B))
+    a, sk, sn, sb = _row_weights(a, N)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((B, J), dtype=torch.float64, device=x.device)
+    da = torch.empty((B, N, K), dtype=x.dtype, device=x.device) if want_da else None
+    check(lib.pa_mixture_rows_fwd_bwd(_dtype(x), int(dist_id), _ptr(x), N, K, B, _ptr(a), sk, sn, sb, _ptr(p0),
+                                      int(s0), int(p0_bs), _ptr(p1), int(s1), int(p1_bs), _ptr(da), _ptr(ws),
+                                      ws.numel(), _ptr(out), _stream()))
+    KP = kp.value
+    return out[:, 0], da, out[:, 1:1 + K], (None if p1 is None else out[:, 1 + KP:1 + KP + K])
+
+
+def mixture_rows_diag_normal_fwd_bwd(x, a, loc, scale, want_da=True):
+    """The per-row-weights leaf for a diagonal Normal over D <= 8 features (pa_mixture_rows_diag_normal_fwd_bwd):
+    x [N, D]; a [B, N, K] or a view of that shape (see _row_weights); loc, scale [B | 1, K | 1, D | 1] (contiguous).
+    -> (S [B], dS/da [B, N, K] in a's dtype or None, dS/dloc [B, K, D], dS/dscale [B, K, D]), the sums in float64 per
+    (b, k, d): a shared parameter takes the sum."""
+    _require_gpu(x, a, loc, scale)
+    N, D = x.shape
+    assert a.dim() == 3 and x.is_contiguous() and loc.is_contiguous() and scale.is_contiguous()
+    assert loc.dim() == 3 and scale.dim() == 3 and a.dtype == x.dtype == loc.dtype == scale.dtype
+    B, _, K = a.shape
+    lib = _lib.load()
+    kp, dd = ctypes.c_int(), ctypes.c_int()
+    J = lib.pa_mixture_rows_diag_normal_layout(K, D, ctypes.byref(kp), ctypes.byref(dd))
+    nbytes = lib.pa_mixture_rows_diag_normal_workspace(K, D, B)
+    if J == 0 or nbytes == 0:
+        raise Unsupported("pyro_amd: mixture_rows_diag_normal_fwd_bwd needs K <= %d, D <= %d, B <= 65535 (K=%d, D=%d, "
+                          "B=%d)" % (MIXTURE_MAX_K, MIXTURE_MAX_D, K, D, B))
+    KP, DD = kp.value, dd.value
+
+    def strides(p):
+        Bp, Kp, Dp = p.shape
+        assert Bp in (1, B) and Kp in (1, K) and Dp in (1, D), (tuple(p.shape), (B, K, D))
+        return (Dp if Kp > 1 else 0), (1 if Dp > 1 else 0), (Kp * Dp if Bp > 1 else 0)
+
+    lk, ld, lb = strides(loc)
+    sk_, sd, sb_ = strides(scale)
+    a, ak, an, ab = _row_weights(a, N)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((B, J), dtype=torch.float64, device=x.device)
+    da = torch.empty((B, N, K), dtype=x.dtype, device=x.device) if want_da else None
+    check(lib.pa_mixture_rows_diag_normal_fwd_bwd(_dtype(x), _ptr(x), N, D, K, B, _ptr(a), ak, an, ab, _ptr(loc), lk,
+                                                  ld, lb, _ptr(scale), sk_, sd, sb_, _ptr(da), _ptr(ws), ws.numel(),
+                                                  _ptr(out), _stream()))
+    dl = out[:, 1:1 + KP * DD].reshape(B, KP, DD)[:, :K, :D]
+    dc = out[:, 1 + KP * DD:].reshape(B, KP, DD)[:, :K, :D]
+    return out[:, 0], da, dl, dc
+
+
 MIXTURE_MVN_MAX_D = 64
 
 

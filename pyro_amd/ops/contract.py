@@ -135,7 +135,7 @@ class LazyMvn(LazyFamily):
         return self.p1
 
 
-FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (_diag_normal, _event, _mvn)
+FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (_diag_normal, _event, _mvn, _rows)
 
 
 @_dispatcher_op("mixture_factor")
@@ -260,12 +260,87 @@ class _MixtureEventFactor(torch.autograd.Function):
         return None, None, g1 * da, to_shape(d0, ctx.shapes[0]), to_shape(d1, ctx.shapes[1])
 
 
+@_dispatcher_op("mixture_rows_factor")
+class _MixtureRowsFactor(torch.autograd.Function):
+    """The mixture leaf with per-row assignment weights (pa_mixture_rows_fwd_bwd): a [B, N, K] (any view; a set-stride
+    of 0: weights shared by the sets); p0 / p1 flat, addressed b * bs + k * s.  ``want_da``: the weights need a
+    gradient -- the responsibilities [B, N, K] are written and kept for the backward, which scales that private buffer
+    in place (one backward per forward: torch refuses a second, the saved tensor having changed); otherwise nothing of
+    size K N exists."""
+
+    @staticmethod
+    def forward(ctx, dist_id, s0, s1, bs0, bs1, want_da, x, a, p0, p1):
+        S, da, d0, d1 = kernels.mixture_rows_fwd_bwd(dist_id, x, a, p0, s0, p1, s1, bs0, bs1, want_da=want_da)
+        dt = a.dtype
+        ctx.strides = (s0, s1, bs0, bs1)
+        ctx.save_for_backward(da, d0.to(dt), None if d1 is None else d1.to(dt))
+        return S.to(dt)
+
+    @staticmethod
+    def backward(ctx, g):
+        da, d0, d1 = ctx.saved_tensors
+        s0, s1, bs0, bs1 = ctx.strides
+        g = g.reshape(-1, 1)
+
+        def param_grad(d, s_, bs):
+            d = g * d                                   # [B, K]
+            if s_ == 0:
+                d = d.sum(1, keepdim=True)
+            if bs == 0:
+                d = d.sum(0, keepdim=True)
+            return d.reshape(-1)
+
+        return (None, None, None, None, None, None, None, None if da is None else da.mul_(g.reshape(-1, 1, 1)),
+                param_grad(d0, s0, bs0), param_grad(d1, s1, bs1) if d1 is not None else None)
+
+
+@_dispatcher_op("mixture_rows_diag_factor")
+class _MixtureRowsDiagFactor(torch.autograd.Function):
+    """The per-row-weights leaf for a diagonal Normal over D <= 8 features (pa_mixture_rows_diag_normal_fwd_bwd):
+    a [B, N, K] (any view); loc / scale [B | 1, K | 1, D | 1]."""
+
+    @staticmethod
+    def forward(ctx, want_da, x, a, loc, scale):
+        S, da, dl, dc = kernels.mixture_rows_diag_normal_fwd_bwd(x, a, loc, scale, want_da=want_da)
+        dt = a.dtype
+        ctx.shapes = (tuple(loc.shape), tuple(scale.shape))
+        ctx.save_for_backward(da, dl.to(dt), dc.to(dt))
+        return S.to(dt)
+
+    @staticmethod
+    def backward(ctx, g):
+        da, dl, dc = ctx.saved_tensors
+        g2 = g.reshape(-1, 1, 1)
+
+        def to_shape(d, shape):
+            d = g2 * d                                  # [B, K, D]
+            for ax in range(3):
+                if shape[ax] == 1 and d.shape[ax] != 1:
+                    d = d.sum(ax, keepdim=True)
+            return d
+
+        return None, None, None if da is None else da.mul_(g2), to_shape(dl, ctx.shapes[0]), to_shape(dc, ctx.shapes[1])
+
+
+def _flat_param(p, K, B):
+    """A scalar leaf's parameter, a [Kp, Bp] view -> (flat tensor addressed b * bs + k * s, s, bs); (None, 0, 0) for
+    no parameter, (False, 0, 0) for a shape the leaves do not take."""
+    if p is None:
+        return None, 0, 0
+    Kp, Bp = p.shape
+    if Kp not in (1, K) or Bp not in (1, B):
+        return False, 0, 0
+    q = p.t().contiguous().reshape(-1)                 # [Bp, Kp] row-major
+    return q, (1 if Kp == K and K > 1 else 0), (Kp if Bp == B and B > 1 else 0)
+
+
 def _try_fused_mixture(terms, sum_ids, contract_frames):
     """The mixture leaf: one enumerated name k, ONE lazy observed-family term over (k, [b,] n), every other term a
-    function of k (and b) alone -- constant along the data plate --, and the data plate n (dim -1) is contracted
-    here; an outer plate b the parameters vary over (vectorised chains / particles) stays, or is summed too when the
-    caller contracts it here as well.  Returns a tensor (0-dim, or the plate block with n summed) or None when the
-    pattern does not match."""
+    function of k (and b) -- constant along the data plate, or, for scalar observations and a diagonal Normal over at
+    most 8 features, varying along it too (per-row assignment weights: the leaves of csrc/mixture_rows.hip) --, and
+    the data plate n (dim -1) is contracted here; an outer plate b the parameters vary over (vectorised chains /
+    particles) stays, or is summed too when the caller contracts it here as well.  Returns a tensor (0-dim, or the
+    plate block with n summed) or None when the pattern does not match."""
     if not FUSED_MIXTURE or len(sum_ids) != 1 or len(terms) < 1:
         return None
     lazy = [t for t in terms if t.tensor is None and isinstance(t.lazy, LazyFamily)]
@@ -286,6 +361,11 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
         return None
     nplates = None
     a = None
+    N = x.shape[0]
+    # per-row weights: the scalar-data families and a diagonal Normal over at most 8 features have a leaf for them
+    rows_ok = not isinstance(lz, LazyMvn) and (lz.D is None or (
+        lz.dist_id == kernels._lib.DIST_NORMAL and lz.D <= kernels.MIXTURE_MAX_D))
+    a_rows = None                                      # the terms that vary along the data plate: [B or 1, N, K]
     for t in dense:
         if t.ids != (kid,) or not isinstance(t.tensor, torch.Tensor) or t.tensor.dtype != x.dtype \
                 or not kernels.on_device(t.tensor) or t.tensor.shape[0] != K:
@@ -295,22 +375,21 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
             nplates = len(blk)
         big = [i - len(blk) for i, s_ in enumerate(blk) if s_ > 1]
         if big and (big != [lz.batch_dim] or blk[lz.batch_dim] != B):
-            return None                                # varies along the data plate (per-row weights) or elsewhere
+            # varies along the data plate (per-row weights) or elsewhere
+            if not rows_ok or blk[-1] != N or any(d != -1 and (d != lz.batch_dim or blk[d] != B) for d in big):
+                return None
+            tr = t.tensor.reshape(K, -1, N).permute(1, 2, 0)        # [B or 1, N, K]: a view of the term
+            a_rows = tr if a_rows is None else a_rows + tr
+            continue
         tk = t.tensor.reshape(K, -1).t()               # [B or 1, K]
         a = tk if a is None else a + tk
+    if a_rows is not None:
+        if a is not None:
+            a_rows = a_rows + a.unsqueeze(1)           # (one broadcast add: the constant terms join the per-row ones)
+        return _fused_mixture_rows(lz, a_rows, frames, nplates)
     if a is None:                                      # no assignment probabilities here
         a = x.new_zeros((1, K))
     a = a.expand(B, K).contiguous()
-
-    def flat(p):
-        # [Kp, Bp] view -> (flat tensor addressed b * bs + k * s, s, bs)
-        if p is None:
-            return None, 0, 0
-        Kp, Bp = p.shape
-        if Kp not in (1, K) or Bp not in (1, B):
-            return False, 0, 0
-        q = p.t().contiguous().reshape(-1)             # [Bp, Kp] row-major
-        return q, (1 if Kp == K and K > 1 else 0), (Kp if Bp == B and B > 1 else 0)
 
     if isinstance(lz, LazyMvn):                        # a full-covariance MultivariateNormal: value [N, D]
         D = lz.D
@@ -331,18 +410,42 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
         S = _MixtureEventFactor.invoke(int(lz.dist_id), x.contiguous(), a, lz.p0.transpose(0, 1).contiguous(),
                                        p1)                                                         # [B]
     else:
-        p0, s0, bs0 = flat(lz.p0)
-        p1, s1, bs1 = flat(lz.p1)
+        p0, s0, bs0 = _flat_param(lz.p0, K, B)
+        p1, s1, bs1 = _flat_param(lz.p1, K, B)
         if p0 is False or p1 is False or p0 is None:
             return None
         S = _MixtureFactor.invoke(int(lz.dist_id), s0, s1, bs0, bs1, x.contiguous(), a, p0, p1)   # [B]
+    return _mixture_plate_block(S, lz, frames, nplates)
+
+
+def _mixture_plate_block(S, lz, frames, nplates):
+    """S [B] of a mixture leaf -> what the contraction returns: 0-dim, or the plate block with n summed."""
     if lz.batch_dim is None or lz.batch_dim in frames:
         return S.sum()                                 # every plate contracted here
     if nplates is None:
         nplates = -lz.batch_dim
     shape = [1] * nplates
-    shape[lz.batch_dim] = B
+    shape[lz.batch_dim] = lz.B
     return S.reshape(shape)
+
+
+def _fused_mixture_rows(lz, a, frames, nplates):
+    """The leaf with per-row weights a [B or 1, N, K] (a view of the terms where there is one term; weights shared by
+    the sets keep a set-stride of 0).  The responsibilities are written only when the weights need a gradient."""
+    x, K, B = lz.value, lz.K, lz.B
+    want_da = bool(a.requires_grad and torch.is_grad_enabled())
+    a = a.expand(B, x.shape[0], K)
+    if lz.D is not None:                               # a diagonal Normal over at most 8 features: value [N, D]
+        S = _MixtureRowsDiagFactor.invoke(want_da, x.contiguous(), a, lz.p0.transpose(0, 1).contiguous(),
+                                          lz.p1.transpose(0, 1).contiguous())                      # [B]
+        return _mixture_plate_block(S, lz, frames, nplates)
+
+    p0, s0, bs0 = _flat_param(lz.p0, K, B)
+    p1, s1, bs1 = _flat_param(lz.p1, K, B)
+    if p0 is False or p1 is False or p0 is None:
+        return None
+    S = _MixtureRowsFactor.invoke(int(lz.dist_id), s0, s1, bs0, bs1, want_da, x.contiguous(), a, p0, p1)   # [B]
+    return _mixture_plate_block(S, lz, frames, nplates)
 
 
 @_dispatcher_op("lda_factor")
