@@ -1177,6 +1177,36 @@ int pa_mixture_rows_diag_normal_fwd_bwd(int dtype, const void* x, int64_t N, int
                                         void* workspace, size_t workspace_bytes, double* out_padded,
                                         pa_stream_t stream);
 
+/* ---- csrc/mixture_assign.hip: the component of every row of a plated mixture, most probable or drawn ---------------
+ * Replaces, for infer_discrete on a plated mixture (pyro/infer/discrete.py _sample_posterior_from_trace): the two
+ * [K, N] log-factors, their add, and the reduction of the [K, N] frame over the enumerated variable by the map /
+ * sample einsum backends (pyro/ops/einsum/torch_map.py, torch_sample.py: an argmax, or a Categorical draw from the
+ * frame's softmax).  With t_k = a[b][n][k] + log p(x[n] | p0[b][k], p1[b][k])            (K <= 64, 1 <= B <= 65535):
+ *   mode 0: z[b][n] = the smallest k with t_k = max_k t_k;
+ *   mode 1: z[b][n] = the smallest k with c_k > u c_{K-1}, clamped to the largest k with e_k > 0, where
+ *           e_k = exp(t_k - max_k t_k), c_k = e_0 + .. + e_k added in index order, and u = element b N + n of the
+ *           uniform stream (seed, offset [+ *offset_dev, for draws under a capture]) in `dtype`, mapped from Philox
+ *           blocks as pa_philox_uniform maps them (f32: four per block, f64: two): one uniform per row, inverse CDF.
+ * A row with no finite term -- every t_k = -inf, or a NaN among them -- gets 0 (as torch.argmax gives).  x, a, p0, p1,
+ * families and dtypes as pa_mixture_rows_fwd_bwd: a[b][n][k] = a[b * a_batch_stride + n * a_stride_n + k * a_stride_k]
+ * (a_stride_n = 0: weights shared by the rows, the plain mixture; a_batch_stride = 0: shared by the sets).  z: B N
+ * int64, row-major, each written once by an ordinary vector store.  One launch, no workspace, bit-reproducible.
+ * Outside the limits: PA_ERR_UNSUPPORTED before any launch. */
+int pa_mixture_assign(int dtype, int dist, const void* x, int64_t N, int K, int64_t B, const void* a,
+                      int64_t a_stride_k, int64_t a_stride_n, int64_t a_batch_stride, const void* p0,
+                      int64_t p0_stride, int64_t p0_batch_stride, const void* p1, int64_t p1_stride,
+                      int64_t p1_batch_stride, int mode, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                      int64_t* z, pa_stream_t stream);
+
+/* The same for a diagonal Normal over D <= 8 features (t_k = a[b][n][k] + sum_d log N(x[n][d] | loc[b][k][d],
+ * scale[b][k][d])): x [N, D] row-major, loc and scale addressed as in pa_mixture_diag_normal_fwd_bwd. */
+int pa_mixture_assign_diag_normal(int dtype, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                                  int64_t a_stride_k, int64_t a_stride_n, int64_t a_batch_stride, const void* loc,
+                                  int64_t loc_stride_k, int64_t loc_stride_d, int64_t loc_batch_stride,
+                                  const void* scale, int64_t scale_stride_k, int64_t scale_stride_d,
+                                  int64_t scale_batch_stride, int mode, uint64_t seed, uint64_t offset,
+                                  const uint64_t* offset_dev, int64_t* z, pa_stream_t stream);
+
 /* ---- csrc/replay.hip: a captured step that is a short chain of kernels, launched as kernels ----------------
  * Replaces nothing of the reference's (its SVI.step, pyro/infer/svi.py:134-162, re-runs the model): it is the
  * replay path of this package's captured step, opt-in on the host side: measured on config 2 a step that waits for

@@ -253,6 +253,13 @@ _SIGNATURES = {
                                                     c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                                     c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                                     c_size_t, c_void_p, c_void_p]),
+    "pa_mixture_assign": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                  c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_uint64, c_uint64,
+                                  c_void_p, c_void_p, c_void_p]),
+    "pa_mixture_assign_diag_normal": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
+                                              c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                              c_int64, c_int64, c_int64, c_int, c_uint64, c_uint64, c_void_p,
+                                              c_void_p, c_void_p]),
     "pa_graph_direct_plan": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
     "pa_graph_direct_launch": (c_int, [c_void_p, c_void_p]),
     "pa_graph_direct_free": (c_int, [c_void_p]),

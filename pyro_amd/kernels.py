@@ -2097,6 +2097,66 @@ def mixture_rows_diag_normal_fwd_bwd(x, a, loc, scale, want_da=True):
     return out[:, 0], da, dl, dc
 
 
+def _assign_weights(a, N):
+    """a [B, K] (weights shared by the rows) or [B, N, K] (per row, any view: see _row_weights) -> (tensor to address,
+    stride_k, stride_n, batch_stride, B, K)."""
+    if a.dim() == 2:
+        B, K = a.shape
+        a = a.contiguous()
+        return a, (1 if K > 1 else 0), 0, (K if B > 1 else 0), B, K
+    assert a.dim() == 3, tuple(a.shape)
+    B, _, K = a.shape
+    return _row_weights(a, N) + (B, K)
+
+
+def mixture_assign(dist_id, x, a, p0, s0, p1, s1, p0_bs=0, p1_bs=0, mode=0, seed=0, offset=0, offset_dev=None):
+    """The component of every row of a plated mixture (pa_mixture_assign), from ONE pass over x: with t[b, n, k] =
+    a[b, (n,) k] + log p(x[n] | p0[b, k], p1[b, k]), ``mode`` 0: the first argmax over k; ``mode`` 1: one draw from
+    softmax_k by inverse CDF on element b N + n of the Philox uniform stream (seed, offset[, offset_dev]) in x's dtype.
+    x [N]; a [B, K] (weights shared by the rows) or [B, N, K] (per row; any layout but component stride 1 or 0 is
+    copied to row-major first, as for mixture_rows_fwd_bwd); p0 / p1 flat, addressed b * bs + k * s as for
+    mixture_fwd_bwd.  -> int64 [B, N]; a row with no finite term gets 0.  Nothing of size K N is allocated."""
+    _require_gpu(x, a, p0, p1, offset_dev)
+    N = x.numel()
+    assert x.is_contiguous() and p0.is_contiguous() and (p1 is None or p1.is_contiguous())
+    assert a.dtype == x.dtype and p0.dtype == x.dtype and (p1 is None or p1.dtype == x.dtype)
+    a, sk, sn, sb, B, K = _assign_weights(a, N)
+    if not (1 <= K <= MIXTURE_MAX_K and 1 <= B <= 65535) or int(dist_id) not in MIXTURE_FAMILIES:
+        raise Unsupported("pyro_amd: mixture_assign needs a family of MIXTURE_FAMILIES, 1 <= K <= %d, "
+                          "1 <= B <= 65535 (family %d, K=%d, B=%d)" % (MIXTURE_MAX_K, int(dist_id), K, B))
+    z = torch.empty((B, N), dtype=torch.int64, device=x.device)
+    check(_lib.load().pa_mixture_assign(_dtype(x), int(dist_id), _ptr(x), N, K, B, _ptr(a), sk, sn, sb, _ptr(p0),
+                                        int(s0), int(p0_bs), _ptr(p1), int(s1), int(p1_bs), int(mode), int(seed),
+                                        int(offset), _ptr(offset_dev), _ptr(z), _stream()))
+    return z
+
+
+def mixture_assign_diag_normal(x, a, loc, scale, mode=0, seed=0, offset=0, offset_dev=None):
+    """mixture_assign for a diagonal Normal over D <= 8 features (pa_mixture_assign_diag_normal): x [N, D]; a [B, K] or
+    [B, N, K]; loc, scale [B | 1, K | 1, D | 1] (contiguous).  -> int64 [B, N]."""
+    _require_gpu(x, a, loc, scale, offset_dev)
+    N, D = x.shape
+    assert x.is_contiguous() and loc.is_contiguous() and scale.is_contiguous()
+    assert loc.dim() == 3 and scale.dim() == 3 and a.dtype == x.dtype == loc.dtype == scale.dtype
+    a, ak, an, ab, B, K = _assign_weights(a, N)
+    if not (1 <= K <= MIXTURE_MAX_K and 1 <= D <= MIXTURE_MAX_D and 1 <= B <= 65535):
+        raise Unsupported("pyro_amd: mixture_assign_diag_normal needs K <= %d, D <= %d, B <= 65535 (K=%d, D=%d, B=%d)"
+                          % (MIXTURE_MAX_K, MIXTURE_MAX_D, K, D, B))
+
+    def strides(p):
+        Bp, Kp, Dp = p.shape
+        assert Bp in (1, B) and Kp in (1, K) and Dp in (1, D), (tuple(p.shape), (B, K, D))
+        return (Dp if Kp > 1 else 0), (1 if Dp > 1 else 0), (Kp * Dp if Bp > 1 else 0)
+
+    lk, ld, lb = strides(loc)
+    sk_, sd, sb_ = strides(scale)
+    z = torch.empty((B, N), dtype=torch.int64, device=x.device)
+    check(_lib.load().pa_mixture_assign_diag_normal(_dtype(x), _ptr(x), N, D, K, B, _ptr(a), ak, an, ab, _ptr(loc), lk,
+                                                    ld, lb, _ptr(scale), sk_, sd, sb_, int(mode), int(seed),
+                                                    int(offset), _ptr(offset_dev), _ptr(z), _stream()))
+    return z
+
+
 MIXTURE_MVN_MAX_D = 64
 
 

@@ -136,6 +136,7 @@ class LazyMvn(LazyFamily):
 
 
 FUSED_MIXTURE = True          # the mixture leaf goes through pa_mixture_fwd_bwd (_diag_normal, _event, _mvn, _rows)
+MAX_PRODUCT = False           # max in place of logsumexp over the enumerated names (see max_product() below)
 
 
 @_dispatcher_op("mixture_factor")
@@ -334,14 +335,14 @@ def _flat_param(p, K, B):
     return q, (1 if Kp == K and K > 1 else 0), (Kp if Bp == B and B > 1 else 0)
 
 
-def _try_fused_mixture(terms, sum_ids, contract_frames):
-    """The mixture leaf: one enumerated name k, ONE lazy observed-family term over (k, [b,] n), every other term a
-    function of k (and b) -- constant along the data plate, or, for scalar observations and a diagonal Normal over at
-    most 8 features, varying along it too (per-row assignment weights: the leaves of csrc/mixture_rows.hip) --, and
-    the data plate n (dim -1) is contracted here; an outer plate b the parameters vary over (vectorised chains /
-    particles) stays, or is summed too when the caller contracts it here as well.  Returns a tensor (0-dim, or the
-    plate block with n summed) or None when the pattern does not match."""
-    if not FUSED_MIXTURE or len(sum_ids) != 1 or len(terms) < 1:
+def _match_mixture(terms, sum_ids, contract_frames):
+    """The pattern of the mixture leaf: one enumerated name k, ONE lazy observed-family term over (k, [b,] n), every
+    other term a function of k (and b) -- constant along the data plate, or, for scalar observations and a diagonal
+    Normal over at most 8 features, varying along it too (per-row assignment weights) --, and the data plate n
+    (dim -1) among ``contract_frames``.  -> (the lazy Term, the constant part a [B or 1, K] or None, the per-row part
+    a_rows [B or 1, N, K] or None, the number of plate dims of the dense terms or None), or None when the pattern does
+    not match.  Shared by the contraction (_try_fused_mixture) and by infer_discrete (infer/discrete.py)."""
+    if not FUSED_MIXTURE or MAX_PRODUCT or len(sum_ids) != 1 or len(terms) < 1:
         return None
     lazy = [t for t in terms if t.tensor is None and isinstance(t.lazy, LazyFamily)]
     dense = [t for t in terms if t.tensor is not None]
@@ -383,6 +384,20 @@ def _try_fused_mixture(terms, sum_ids, contract_frames):
             continue
         tk = t.tensor.reshape(K, -1).t()               # [B or 1, K]
         a = tk if a is None else a + tk
+    return lazy[0], a, a_rows, nplates
+
+
+def _try_fused_mixture(terms, sum_ids, contract_frames):
+    """The mixture leaf (the pattern: _match_mixture); the data plate n (dim -1) is contracted here; an outer plate b
+    the parameters vary over (vectorised chains / particles) stays, or is summed too when the caller contracts it here
+    as well.  Returns a tensor (0-dim, or the plate block with n summed) or None when the pattern does not match."""
+    match = _match_mixture(terms, sum_ids, contract_frames)
+    if match is None:
+        return None
+    lazy_term, a, a_rows, nplates = match
+    lz = lazy_term.lazy
+    frames = {f.dim for f in contract_frames}
+    x, K, B = lz.value, lz.K, lz.B
     if a_rows is not None:
         if a is not None:
             a_rows = a_rows + a.unsqueeze(1)           # (one broadcast add: the constant terms join the per-row ones)
@@ -609,6 +624,14 @@ def _sumproduct(terms, sum_ids):
     drop = [i for i, v in enumerate(ids) if v in sum_ids]
     keep_ids = [v for v in ids if v not in sum_ids]
     aligned = [align(t, ids) for t in terms]
+    if MAX_PRODUCT:
+        # max-product: plate products stay sums; torch.max(dim) hands its gradient to ONE maximiser
+        total = None
+        for x in aligned:
+            total = x if total is None else total + x
+        for d in reversed(drop):
+            total = total.max(dim=d).values
+        return total, keep_ids
     if FUSED_SUMPRODUCT and len(drop) == 1 and 1 <= len(aligned) <= 4:
         x0 = aligned[0]
         ok = all(isinstance(x, torch.Tensor) and x.dtype == x0.dtype and x.device == x0.device
@@ -762,10 +785,10 @@ def _contract_component(tensor_tree, sum_ids, reduce_all=False, keep_dims=()):
             # (keep_dims: plate dims the caller does NOT sum -- the chain plate of a vectorised potential)
             fuse_frames = frozenset(f for f in leaf if f.dim not in keep_dims) \
                 if (reduce_all and parent == leaf) else contract_frames
-            fused = _try_fused_lda(terms, ids, fuse_frames)
+            fused = None if MAX_PRODUCT else _try_fused_lda(terms, ids, fuse_frames)
             if fused is None:
                 fused = _try_fused_mixture(terms, ids, fuse_frames)
-            chain = _try_fused_chain(terms, ids) if fused is None and FUSED_CHAIN else None
+            chain = _try_fused_chain(terms, ids) if fused is None and FUSED_CHAIN and not MAX_PRODUCT else None
             if fused is not None:
                 tensor, new_ids = fused, []
             elif chain is not None:
@@ -778,6 +801,22 @@ def _contract_component(tensor_tree, sum_ids, reduce_all=False, keep_dims=()):
     ordinal, terms = tensor_tree.popitem()
     tensor, ids = _sumproduct(terms, set())
     return ordinal, Term(tensor, ids, ordinal)
+
+
+class max_product:
+    """``with max_product():`` -- the contractions inside take the MAXIMUM over the enumerated names where they take
+    the logsumexp otherwise (plate products stay sums), and the fused logsumexp kernels are off: the result is the
+    log-probability of the most probable joint assignment, and its gradient with respect to a log-factor is the
+    indicator of ONE such assignment (torch.max hands the gradient to a single index): the backtrace of Viterbi /
+    max-product message passing (reference: pyro/ops/einsum/torch_map.py with pyro/ops/rings.py MapRing)."""
+
+    def __enter__(self):
+        global MAX_PRODUCT
+        self._keep, MAX_PRODUCT = MAX_PRODUCT, True
+
+    def __exit__(self, *exc):
+        global MAX_PRODUCT
+        MAX_PRODUCT = self._keep
 
 
 def contract_tensor_tree(tensor_tree, sum_ids, reduce_all=False, keep_dims=()):
