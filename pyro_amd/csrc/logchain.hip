@@ -23,6 +23,15 @@ constexpr int LC_MAXK = 64;
 
 template <typename T>
 __device__ __forceinline__ T lc_neg_inf() { return -std::numeric_limits<T>::infinity(); }
+template <typename T>
+__device__ __forceinline__ T lc_pos_inf() { return std::numeric_limits<T>::infinity(); }
+// +inf potentials follow torch.logsumexp, as lse_fwd_kernel (logsumexp.hip) does: a sum that holds a +inf term
+// is +inf -- the shift by the maximum would form exp(inf - inf).  Decided once per sum from its maximum, never
+// per term: with a +inf maximum the terms are summed unshifted (lse_shift), so +inf and finite terms give +inf
+// and a NaN term still gives NaN.  The online sum of the generic body cannot tell a NaN term from a second
+// +inf once its maximum is +inf: there +inf wins (lse_value).
+template <typename T>
+__device__ __forceinline__ T lse_shift(T m) { return m == lc_pos_inf<T>() ? T(0) : m; }
 
 // online log-sum-exp accumulation of value v into (m, s)
 template <typename T>
@@ -37,7 +46,7 @@ __device__ __forceinline__ void lse_push(T v, T& m, T& s) {
 }
 template <typename T>
 __device__ __forceinline__ T lse_value(T m, T s) {
-  return m == lc_neg_inf<T>() ? m : m + t_log(s);
+  return (m == lc_neg_inf<T>() || m == lc_pos_inf<T>()) ? m : m + t_log(s);
 }
 
 // U[B, T, K]; P[b, t] = P + b * spb + t * spt, row-major [K, K] (i = state at t, j = state at t+1);
@@ -83,9 +92,10 @@ __global__ __launch_bounds__(64) void logchain_kernel(const T* __restrict__ U,
     const T other = __shfl_xor(mz, o, 64);
     mz = other > mz ? other : mz;
   }
-  T sz = (act && a != NEG) ? t_exp(a - mz) : T(0);
+  const T shz = lse_shift(mz);
+  T sz = (act && a != NEG) ? t_exp(a - shz) : T(0);
   for (int o = 32; o > 0; o >>= 1) sz += __shfl_xor(sz, o, 64);
-  const T lz = mz == NEG ? NEG : mz + t_log(sz);
+  const T lz = mz == NEG ? NEG : shz + t_log(sz);
   if (j == 0) logZ[b] = lz;
 
   // ---- backward: beta recursion, posteriors ---------------------------------------------------
@@ -151,11 +161,14 @@ __global__ __launch_bounds__(64) void logchain_lanes_kernel(const T* __restrict_
   T* gb = gamma + b * (int64_t)Tn * K;
   T* xb = xi + b * (int64_t)(Tn - 1) * K * K;
   bool cok[NI];                         // is the q-th index of this lane's chunk a state?
-  int cc[NI];
+  int cc[NI], sc[NI];                   // its index clamped for the loads / the lane its alpha (w) is read from
 #pragma unroll
   for (int q = 0; q < NI; ++q) {
     cok[q] = g * NI + q < K;
     cc[q] = cok[q] ? g * NI + q : 0;
+    // a padded term reads lane K, which holds -inf (x = K is not a state): -inf + -inf stays -inf, where state
+    // 0's value would turn the padding into NaN once it is +inf
+    sc[q] = cok[q] ? g * NI + q : K;
   }
   // log-sum-exp of the NI terms of every lane of a column, over the G chunks: the same value in all of them
   auto lse_chunks = [&](const T (&v)[NI]) {
@@ -167,12 +180,13 @@ __global__ __launch_bounds__(64) void logchain_lanes_kernel(const T* __restrict_
       const T other = __shfl_xor(m, o, 64);
       m = other > m ? other : m;
     }
+    const T sh = lse_shift(m);
     T s = T(0);
 #pragma unroll
-    for (int q = 0; q < NI; ++q) s += v[q] == NEG ? T(0) : t_exp(v[q] - m);
+    for (int q = 0; q < NI; ++q) s += v[q] == NEG ? T(0) : t_exp(v[q] - sh);
 #pragma unroll
     for (int o = KP; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
-    return m == NEG ? NEG : m + t_log(s);
+    return m == NEG ? NEG : sh + t_log(s);
   };
 
   // ---- forward: lane (j = x, chunk g of i) ------------------------------------------------------
@@ -198,7 +212,7 @@ __global__ __launch_bounds__(64) void logchain_lanes_kernel(const T* __restrict_
       if (t < Tn) {                                            // (wave-uniform)
         T v[NI];
 #pragma unroll
-        for (int q = 0; q < NI; ++q) v[q] = __shfl(a, cc[q], 64) + pre[d][q];
+        for (int q = 0; q < NI; ++q) v[q] = __shfl(a, sc[q], 64) + pre[d][q];
         const T u = ub[d];
         if (t + D < Tn) load_fwd(t + D, pre[d], ub[d]);
         const T r = lse_chunks(v);
@@ -214,9 +228,10 @@ __global__ __launch_bounds__(64) void logchain_lanes_kernel(const T* __restrict_
     const T other = __shfl_xor(mz, o, 64);
     mz = other > mz ? other : mz;
   }
-  T sz = az != NEG ? t_exp(az - mz) : T(0);
+  const T shz = lse_shift(mz);
+  T sz = az != NEG ? t_exp(az - shz) : T(0);
   for (int o = 32; o > 0; o >>= 1) sz += __shfl_xor(sz, o, 64);
-  const T lz = mz == NEG ? NEG : mz + t_log(sz);
+  const T lz = mz == NEG ? NEG : shz + t_log(sz);
   if (l == 0) logZ[b] = lz;
   // alpha was written by the owners and is read back by every chunk of the column
   __threadfence_block();
@@ -248,7 +263,7 @@ __global__ __launch_bounds__(64) void logchain_lanes_kernel(const T* __restrict_
         const T at = xok ? abuf[d] : NEG;
         T v[NI];
 #pragma unroll
-        for (int q = 0; q < NI; ++q) v[q] = pre[d][q] + __shfl(wv, cc[q], 64);     // P[x, j] + w[j]
+        for (int q = 0; q < NI; ++q) v[q] = pre[d][q] + __shfl(wv, sc[q], 64);     // P[x, j] + w[j]
         if (t - D >= 0) load_bwd(t - D, pre[d], ub[d], abuf[d]);
         if (xok) {
           T* xt = xb + (int64_t)t * K * K + (int64_t)x * K + g * NI;

@@ -573,6 +573,10 @@ def logchain_fwd_bwd(unary, pairwise):
         beta[:, t] = logsumexp(Pn[:, t] + w[:, None, :], axis=2)
         xi[:, t] = np.exp(alpha[:, t, :, None] + Pn[:, t] + w[:, None, :] - lz[:, None, None])
     gamma = np.exp(alpha + beta - lz[:, None, None])
+    # an impossible chain (logZ = -inf) has no posterior: 0, the kernels' sum-product convention
+    dead = np.isneginf(lz)
+    gamma[dead] = 0.0
+    xi[dead] = 0.0
     mk = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=unary.dtype)   # noqa: E731
     return mk(lz), mk(gamma), mk(xi)
 

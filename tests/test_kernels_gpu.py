@@ -1103,6 +1103,13 @@ def test_lda_factor_minus_inf_column(gpu):
     r_out, r_gt, r_gp = o_lda.lda_factor(words.cpu().numpy(), lt.cpu().numpy(), lp.cpu().numpy())
     np.testing.assert_allclose(out.cpu().numpy(), r_out)   # includes a -inf document
     assert not torch.isnan(gt).any() and not torch.isnan(gp).any()
+    # the impossible pair (word 2 in document 0) has no responsibility: 0, not NaN; the others their values
+    np.testing.assert_allclose(gt.cpu().numpy(), r_gt, rtol=1e-13, atol=1e-15)
+    np.testing.assert_allclose(gp.cpu().numpy(), r_gp, rtol=1e-13, atol=1e-15)
+    from tests import enum_edge_cases as ec
+    ref = ec.lda_reference(words.cpu(), lt.cpu(), lp.cpu())
+    ec.lda_check("lda/atomic/TMAX8/f64", [x.cpu().numpy() for x in (out, gt, gp)],
+                 {"ref": [x.numpy() for x in ref[:3]], "M": [x.numpy() for x in ref[3:]], "cpu32": None}, False)
 
 
 # ---------------------------------------------------------------------------------------------
