@@ -1207,6 +1207,29 @@ int pa_mixture_assign_diag_normal(int dtype, const void* x, int64_t N, int D, in
                                   int64_t scale_batch_stride, int mode, uint64_t seed, uint64_t offset,
                                   const uint64_t* offset_dev, int64_t* z, pa_stream_t stream);
 
+/* ---- csrc/mixture_assign_wide.hip: the same for the two wide leaves, weights shared by the rows ----------------------
+ * Replaces, for infer_discrete on a mixture whose observation is `Fam(p0[z], p1[z]).to_event(1)` or
+ * `MultivariateNormal(locs[z], scale_tril=L[z])`: the observed site's [K, N, D] frame (torch's Independent.log_prob /
+ * MultivariateNormal.log_prob), the add of the enumerated site's log-probabilities and the map / sample reduction over
+ * the enumerated variable.  t_k = a[b][k] + log p(x[n] | component k of set b); mode, seed, offset, offset_dev, z and
+ * the rule (first maximum; inverse CDF at uniform b N + n, clamped to the last nonzero term; 0 for a row with a NaN or
+ * no finite term) as pa_mixture_assign, decided in double.  One launch, one pass over x, no workspace, nothing of
+ * size K N, bit-reproducible.  Outside the limits: PA_ERR_UNSUPPORTED before any launch.
+ * pa_mixture_assign_event: families, x, a, p0 and p1 as pa_mixture_event_fwd_bwd (1 <= D <= 1024, K <= 64,
+ * 1 <= B <= 65535; scores per chunk of features in `dtype`, across chunks in double). */
+int pa_mixture_assign_event(int dtype, int dist, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                            int64_t a_batch_stride, const void* p0, int64_t p0_stride_k, int64_t p0_stride_d,
+                            int64_t p0_batch_stride, const void* p1, int64_t p1_stride_k, int64_t p1_stride_d,
+                            int64_t p1_batch_stride, int mode, uint64_t seed, uint64_t offset,
+                            const uint64_t* offset_dev, int64_t* z, pa_stream_t stream);
+
+/* pa_mixture_assign_mvn: x, a, loc and w (= the inverse of the scale_tril) as pa_mixture_mvn_fwd_bwd (1 <= D <= 64,
+ * K <= 64, 1 <= B <= 65535; d = x - loc formed before the product, scores in `dtype`). */
+int pa_mixture_assign_mvn(int dtype, const void* x, int64_t N, int D, int K, int64_t B, const void* a,
+                          int64_t a_batch_stride, const void* loc, int64_t loc_stride_k, int64_t loc_batch_stride,
+                          const void* w, int64_t w_stride_k, int64_t w_batch_stride, int mode, uint64_t seed,
+                          uint64_t offset, const uint64_t* offset_dev, int64_t* z, pa_stream_t stream);
+
 /* ---- csrc/replay.hip: a captured step that is a short chain of kernels, launched as kernels ----------------
  * Replaces nothing of the reference's (its SVI.step, pyro/infer/svi.py:134-162, re-runs the model): it is the
  * replay path of this package's captured step, opt-in on the host side: measured on config 2 a step that waits for

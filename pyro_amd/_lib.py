@@ -260,6 +260,12 @@ _SIGNATURES = {
                                               c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                               c_int64, c_int64, c_int64, c_int, c_uint64, c_uint64, c_void_p,
                                               c_void_p, c_void_p]),
+    "pa_mixture_assign_event": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64,
+                                        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                        c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "pa_mixture_assign_mvn": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p,
+                                      c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_uint64, c_uint64,
+                                      c_void_p, c_void_p, c_void_p]),
     "pa_graph_direct_plan": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
     "pa_graph_direct_launch": (c_int, [c_void_p, c_void_p]),
     "pa_graph_direct_free": (c_int, [c_void_p]),

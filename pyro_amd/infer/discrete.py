@@ -12,8 +12,10 @@ Two routes, site by site in the order the model visits them:
     far can be extended with -- fixing the sites one after another therefore ends at a joint maximiser, ties included;
   * fast -- a plated mixture: the site's factors are exactly its own prior (constant along the data plate or per row)
     and ONE observed family term the mixture leaf matches (scalar data of kernels.MIXTURE_FAMILIES, or a diagonal
-    Normal over at most 8 features; an outer plate of parameter sets is optional): kernels.mixture_assign* picks or
-    draws every row's component in one pass, and nothing of size K N exists beyond the caller's own per-row weights.
+    Normal over at most 8 features; with weights shared by the rows also any of those families over at most 1024
+    features through ``.to_event(1)`` and a full-covariance MultivariateNormal over at most 64; an outer plate of
+    parameter sets is optional): kernels.mixture_assign* picks or draws every row's component in one pass, and
+    nothing of size K N (let alone K N D) exists beyond the caller's own per-row weights.
     ``ops.contract.FUSED_MIXTURE = False`` turns it off.
 Both routes draw from the same uniforms in the same way, so at a fixed seed they return the same values.
 """
@@ -27,6 +29,12 @@ from ..ops import contract
 from ..poutine.util import prune_subsample_sites
 from .traceenum_elbo import (BackwardSample, _enum_log_prob, _enum_sites, _evidence_of, _lazy_family, _ordinal,
                              _packed, _posterior_of, _posterior_weights, _support_last)
+
+
+def _wide_assign_ready(x):
+    """Whether the wide leaves' assignment kernels (kernels.mixture_assign_event / mixture_assign_mvn) can take the
+    observation ``x``: they run on the device only."""
+    return x.is_cuda
 
 
 def _uniform(shape, dtype, device, on_device):
@@ -138,20 +146,25 @@ class _InferDiscrete(BackwardSample):
             if lazy is not None or other in self.enum_names:
                 return None                   # a second factor, or a second enumerated site sharing one
             got = _lazy_family(node, fed)
-            if got is None or got[0] != kid or isinstance(got[1], contract.LazyMvn):
+            if got is None or got[0] != kid:
                 return None
             lazy = contract.Term(None, (kid,), _ordinal(node), lazy=got[1])
         if lazy is None or lazy.ordinal != _ordinal(site):
             return None
         lz = lazy.lazy
-        diag = lz.D is not None
-        if diag and not (lz.dist_id == kernels._lib.DIST_NORMAL and lz.D <= kernels.MIXTURE_MAX_D):
-            return None                       # the wide event-shaped leaves have no assignment kernel
+        mvn = isinstance(lz, contract.LazyMvn)
+        diag = not mvn and lz.D is not None and lz.dist_id == kernels._lib.DIST_NORMAL and lz.D <= kernels.MIXTURE_MAX_D
+        wide = lz.D is not None and not diag  # an event-shaped or full-covariance leaf: weights shared by the rows
+        if wide and not (_wide_assign_ready(lz.value) and
+                         lz.D <= (kernels.MIXTURE_MVN_MAX_D if mvn else kernels.MIXTURE_EVENT_MAX_D)):
+            return None
         own = _packed(site, _enum_log_prob(site).detach(), fed)
         match = contract._match_mixture([own, lazy], {kid}, lazy.ordinal)
         if match is None:
             return None
         _, a, a_rows, _ = match
+        if wide and (a_rows is not None or a is None):
+            return None
         x, K, B = lz.value, lz.K, lz.B
         N = x.shape[0]
         if a_rows is not None:
@@ -159,7 +172,20 @@ class _InferDiscrete(BackwardSample):
         else:
             w = a.expand(B, K)
         seed, off, off_dev = rng.reserve(B * N, x.dtype) if self.temperature == 1 else (0, 0, None)
-        if diag:
+        if mvn:
+            # W = L^-1 formed in float64, as the contraction forms it for the leaf (contract._try_fused_mixture)
+            L = lz.scale_tril.detach().transpose(0, 1)
+            eye = torch.eye(lz.D, dtype=torch.float64, device=L.device)
+            W = torch.linalg.solve_triangular(L.to(torch.float64), eye, upper=False).to(x.dtype)
+            z = kernels.mixture_assign_mvn(x.contiguous(), w.contiguous(),
+                                           lz.loc.detach().transpose(0, 1).contiguous(), W.contiguous(),
+                                           mode=self.temperature, seed=seed, offset=off, offset_dev=off_dev)
+        elif wide:
+            p1 = None if lz.p1 is None else lz.p1.detach().transpose(0, 1).contiguous()
+            z = kernels.mixture_assign_event(int(lz.dist_id), x.contiguous(), w.contiguous(),
+                                             lz.p0.detach().transpose(0, 1).contiguous(), p1,
+                                             mode=self.temperature, seed=seed, offset=off, offset_dev=off_dev)
+        elif diag:
             z = kernels.mixture_assign_diag_normal(x.contiguous(), w, lz.p0.detach().transpose(0, 1).contiguous(),
                                                    lz.p1.detach().transpose(0, 1).contiguous(),
                                                    mode=self.temperature, seed=seed, offset=off, offset_dev=off_dev)

@@ -2242,6 +2242,74 @@ def mixture_event_fwd_bwd(dist_id, x, a, p0, p1):
     return S, da, g0, g1
 
 
+def _shared_weights(a):
+    """a [B, K], weights shared by the rows -> (contiguous tensor, batch stride, B, K)"""
+    assert a.dim() == 2, tuple(a.shape)
+    B, K = a.shape
+    return a.contiguous(), (K if B > 1 else 0), B, K
+
+
+def mixture_assign_event(dist_id, x, a, p0, p1, mode=0, seed=0, offset=0, offset_dev=None):
+    """mixture_assign for an event-shaped observation ``Fam(p0[z], p1[z]).to_event(1)`` over D <= 1024 features
+    (pa_mixture_assign_event), every family of MIXTURE_FAMILIES, from ONE pass over x: x [N, D]; a [B, K] (weights
+    shared by the rows); p0, p1 [B | 1, K | 1, D | 1] (contiguous, of x's dtype; p1 None for the one-parameter
+    families), as for mixture_event_fwd_bwd.  -> int64 [B, N].  Nothing of size K N is allocated."""
+    _require_gpu(x, a, p0, p1, offset_dev)
+    N, D = x.shape
+    assert x.is_contiguous() and p0.is_contiguous() and (p1 is None or p1.is_contiguous())
+    assert p0.dim() == 3 and (p1 is None or p1.dim() == 3)
+    assert a.dtype == x.dtype == p0.dtype and (p1 is None or p1.dtype == x.dtype)
+    a, ab, B, K = _shared_weights(a)
+    if not (1 <= K <= MIXTURE_MAX_K and 1 <= D <= MIXTURE_EVENT_MAX_D and 1 <= B <= 65535 and N >= 1) \
+            or int(dist_id) not in MIXTURE_FAMILIES or x.dtype not in (torch.float32, torch.float64):
+        raise Unsupported("pyro_amd: mixture_assign_event needs a family of MIXTURE_FAMILIES, 1 <= K <= %d, "
+                          "1 <= D <= %d, 1 <= B <= 65535, N >= 1, float32 or float64 (dist=%d, K=%d, D=%d, B=%d, N=%d)"
+                          % (MIXTURE_MAX_K, MIXTURE_EVENT_MAX_D, int(dist_id), K, D, B, N))
+    npar = 2 if int(dist_id) in (_lib.DIST_NORMAL, _lib.DIST_LOG_NORMAL, _lib.DIST_GAMMA) else 1
+    if (p1 is None) != (npar == 1):
+        raise Unsupported("pyro_amd: mixture_assign_event: family %d takes %d parameter(s)" % (int(dist_id), npar))
+
+    def strides(p):
+        if p is None:
+            return 0, 0, 0
+        Bp, Kp, Dp = p.shape
+        assert Bp in (1, B) and Kp in (1, K) and Dp in (1, D), (tuple(p.shape), (B, K, D))
+        return (Dp if Kp > 1 else 0), (1 if Dp > 1 else 0), (Kp * Dp if Bp > 1 else 0)
+
+    k0, d0, b0 = strides(p0)
+    k1, d1, b1 = strides(p1)
+    z = torch.empty((B, N), dtype=torch.int64, device=x.device)
+    check(_lib.load().pa_mixture_assign_event(_dtype(x), int(dist_id), _ptr(x), N, D, K, B, _ptr(a), ab, _ptr(p0), k0,
+                                              d0, b0, _ptr(p1) if p1 is not None else None, k1, d1, b1, int(mode),
+                                              int(seed), int(offset), _ptr(offset_dev), _ptr(z), _stream()))
+    return z
+
+
+def mixture_assign_mvn(x, a, loc, W, mode=0, seed=0, offset=0, offset_dev=None):
+    """mixture_assign for a full-covariance MultivariateNormal over D <= 64 features (pa_mixture_assign_mvn): x [N, D];
+    a [B, K] (weights shared by the rows); loc [B | 1, K | 1, D]; W [B | 1, K | 1, D, D] = the inverse of the
+    scale_tril, all contiguous and of x's dtype, as for mixture_mvn_fwd_bwd.  -> int64 [B, N]."""
+    _require_gpu(x, a, loc, W, offset_dev)
+    N, D = x.shape
+    assert x.is_contiguous() and loc.is_contiguous() and W.is_contiguous()
+    assert loc.dim() == 3 and W.dim() == 4 and a.dtype == x.dtype == loc.dtype == W.dtype
+    a, ab, B, K = _shared_weights(a)
+    if not (1 <= K <= MIXTURE_MAX_K and 1 <= D <= MIXTURE_MVN_MAX_D and 1 <= B <= 65535 and N >= 1) \
+            or x.dtype not in (torch.float32, torch.float64):
+        raise Unsupported("pyro_amd: mixture_assign_mvn needs 1 <= K <= %d, 1 <= D <= %d, 1 <= B <= 65535, N >= 1, "
+                          "float32 or float64 (K=%d, D=%d, B=%d, N=%d)" % (MIXTURE_MAX_K, MIXTURE_MVN_MAX_D, K, D, B, N))
+    Bl, Kl, Dl = loc.shape
+    Bw, Kw, D1, D2 = W.shape
+    assert Bl in (1, B) and Kl in (1, K) and Dl == D and Bw in (1, B) and Kw in (1, K) and D1 == D2 == D, (
+        tuple(loc.shape), tuple(W.shape), (B, K, D))
+    z = torch.empty((B, N), dtype=torch.int64, device=x.device)
+    check(_lib.load().pa_mixture_assign_mvn(_dtype(x), _ptr(x), N, D, K, B, _ptr(a), ab, _ptr(loc),
+                                            D if Kl > 1 else 0, Kl * D if Bl > 1 else 0, _ptr(W),
+                                            D * D if Kw > 1 else 0, Kw * D * D if Bw > 1 else 0, int(mode), int(seed),
+                                            int(offset), _ptr(offset_dev), _ptr(z), _stream()))
+    return z
+
+
 def lda_factor_fwd_bwd(words, log_theta, log_phi, index=None):
     """words int64 [Wd,B]; log_theta [B,T]; log_phi [T,V] -> (out_doc[B], g_theta[B,T], g_phi[T,V]).
     ``index``: an image from lda_build_index (default: the cached one of ``words``, if any)."""

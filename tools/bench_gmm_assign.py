@@ -1,12 +1,15 @@
-"""Asking a fitted mixture for its clustering, N = 1e6 rows, K = 16 components, f32 (developer tool): infer_discrete at
-temperature 0 and 1 with the assignment kernel (csrc/mixture_assign.hip) and with ``contract.FUSED_MIXTURE = False``
+"""Asking a fitted mixture for its clustering, K = 16 components, f32 (developer tool): infer_discrete at
+temperature 0 and 1 with the assignment kernels (csrc/mixture_assign.hip, csrc/mixture_assign_wide.hip) and with
+``contract.FUSED_MIXTURE = False``
 (the generic route), and -- for temperature 1 -- TraceEnum_ELBO.sample_posterior on the same model, the only route the
 package had before.  Public interface only: on a commit without infer_discrete the file prints the sample_posterior
 column alone -- the baseline.
 
-    python tools/bench_gmm_assign.py [--cases N:K:D,...]
+    python tools/bench_gmm_assign.py [--cases [bern:|mvn:]N:K:D,...]
 
-D = 0: scalar Normal observations; D > 0: a diagonal Normal over D features.  Per case and route: milliseconds per
+D = 0: scalar Normal observations; D > 0: a diagonal Normal over D features; ``bern:`` binarised images under
+``Bernoulli(logits=l[z]).to_event(1)``; ``mvn:`` ``MultivariateNormal(locs[z], scale_tril=L[z])`` (for these two the
+sample_posterior column is left out, and a route that runs out of device memory is reported as such).  Per case and route: milliseconds per
 call as the median of 7 blocks of 3 calls after 2 warm-up calls, with the fastest and slowest block (the run-to-run
 spread a difference has to exceed); each block ends with a device synchronisation, so a number covers the host work,
 every launch and the device time of one call.  Peak device memory of one call above what was allocated before it, by
@@ -29,7 +32,7 @@ try:
 except ImportError:                    # a commit before infer_discrete: the baseline column only
     infer_discrete = None
 
-CASES = "1000000:16:0,1000000:16:8"
+CASES = "1000000:16:0,1000000:16:8,bern:100000:16:784,mvn:1000000:16:32"
 
 
 def blocks(fn, warm=2, nblk=7, per=3):
@@ -75,6 +78,33 @@ def make_mixture(N, K, D, dev):
     return model, x
 
 
+def make_wide_mixture(kind, N, K, D, dev):
+    g = torch.Generator().manual_seed(0)
+    z = torch.randint(0, K, (N,), generator=g)
+    pi = torch.softmax(torch.randn(K, generator=g), -1).to(dev)
+    if kind == "bern":
+        logits = 2.0 * torch.randn(K, D, generator=g)
+        x = torch.bernoulli(torch.sigmoid(logits[z]), generator=g).to(dev)
+        logits = (logits + 0.1 * torch.randn(K, D, generator=g)).to(dev)
+        obs = lambda zz: dist.Bernoulli(logits=logits[zz]).to_event(1)               # noqa: E731
+    else:
+        centres = 3.0 * torch.randn(K, D, generator=g)
+        x = (centres[z] + torch.randn(N, D, generator=g)).to(dev)
+        locs = (centres + 0.1 * torch.randn(K, D, generator=g)).to(dev)
+        L = torch.tril(0.3 / D ** 0.5 * torch.randn(K, D, D, generator=g), -1) + \
+            torch.diag_embed(0.8 + 0.4 * torch.rand(K, D, generator=g))
+        L = L.to(dev)
+        obs = lambda zz: dist.MultivariateNormal(locs[zz], scale_tril=L[zz])       # noqa: E731
+
+    def model(x):
+        with pyro.plate("data", N):
+            zz = pyro.sample("z", dist.Categorical(pi), infer={"enumerate": "parallel"})
+            pyro.sample("x", obs(zz), obs=x)
+        return zz
+
+    return model, x
+
+
 def with_leaf(leaf, fn):
     def call():
         contract.FUSED_MIXTURE = leaf
@@ -86,9 +116,15 @@ def with_leaf(leaf, fn):
 
 
 def report(tag, route, fn):
-    z = fn()
-    assert z.shape[-1] == int(tag.split()[0].split("=")[1]) and z.dtype == torch.int64
-    (med, lo, hi), mem = blocks(fn), peak_of(fn)
+    try:
+        z = fn()
+        assert z.shape[-1] == int(tag.split()[0].split("=")[1]) and z.dtype == torch.int64
+        del z
+        (med, lo, hi), mem = blocks(fn), peak_of(fn)
+    except torch.OutOfMemoryError:
+        torch.cuda.empty_cache()
+        print("%-22s %-42s OUT OF MEMORY" % (tag, route), flush=True)
+        return
     print("%-22s %-42s %9.3f ms (blocks %9.3f .. %9.3f) %7.0f MB" % (tag, route, med, lo, hi, mem), flush=True)
 
 
@@ -99,17 +135,19 @@ def main():
     dev = torch.device("cuda:0")
     pyro.enable_validation(False)
     for case in args.cases.split(","):
-        N, K, D = (int(v) for v in case.split(":"))
-        model, x = make_mixture(N, K, D, dev)
-        tag = "N=%d K=%d D=%d" % (N, K, D)
+        kind = case.split(":")[0] if case[0].isalpha() else None
+        N, K, D = (int(v) for v in case.split(":")[-3:])
+        model, x = make_mixture(N, K, D, dev) if kind is None else make_wide_mixture(kind, N, K, D, dev)
+        tag = "N=%d K=%d D=%d%s" % (N, K, D, "" if kind is None else " " + kind)
         if infer_discrete is not None:
             for temperature in (0, 1):
                 fn = infer_discrete(model, first_available_dim=-2, temperature=temperature)
                 report(tag, "infer_discrete T=%d, assignment kernel" % temperature, with_leaf(True, lambda: fn(x)))
                 report(tag, "infer_discrete T=%d, FUSED_MIXTURE = False" % temperature,
                        with_leaf(False, lambda: fn(x)))
-        elbo = TraceEnum_ELBO(max_plate_nesting=1)
-        report(tag, "sample_posterior (T=1)", lambda: elbo.sample_posterior(model, lambda x: None, x))
+        if kind is None:
+            elbo = TraceEnum_ELBO(max_plate_nesting=1)
+            report(tag, "sample_posterior (T=1)", lambda: elbo.sample_posterior(model, lambda x: None, x))
         del model, x
         torch.cuda.empty_cache()
 
