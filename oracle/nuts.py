@@ -33,6 +33,45 @@ def logaddexp(x, y):
     return math.log1p(math.exp(mn - mx)) + mx if mx > -math.inf else mx
 
 
+class Margins:
+    """Optional recorder (``margins=`` of nuts_transition / find_step_gaussian; off by default, and
+    recording changes nothing that is computed): the smallest distance of every data-dependent
+    decision of one transition from its threshold, per kind --
+      "draw"     |u - prob| of the merge and accept draws,
+      "direction" |u - 0.5| of the direction draws (0.5 is exact in every precision),
+      "turn"     |dot| / (|r| |rho|) of a U-turn test (of the dots that decide it: the largest margin
+                 among the non-positive ones when it turns, the smallest of both when it does not),
+      "diverge"  |sliced - MAX_SLICED_ENERGY|,
+      "slice"    |sliced| (slice sampler: the leaf is inside the slice or not),
+      "find_step" |threshold + delta| of a step-size trial.
+    A lower-precision evaluation of the same transition can decide differently only where a margin is
+    within its rounding error.  ``nan_energy`` / ``nonfinite_energy`` count the leaves whose energy was
+    NaN (the NaN -> +inf branch) / not finite.  With ``trace=True`` the compared quantities themselves
+    (the probability, the cosines, the sliced energy, delta) are kept in order, so that two evaluations
+    of one transition can be compared decision by decision."""
+
+    def __init__(self, trace=False):
+        self.min = {}
+        self.nan_energy = 0
+        self.nonfinite_energy = 0
+        self.trace = [] if trace else None
+
+    def note(self, kind, value, *quantities):
+        value = float(value)
+        if value == value and value < self.min.get(kind, math.inf):
+            self.min[kind] = value
+        if self.trace is not None:
+            self.trace += [(kind, float(q)) for q in quantities]
+
+    def smallest(self):
+        return min(self.min.values(), default=math.inf)
+
+
+def _cosine(dot, a, b):
+    den = math.sqrt(float(a.dot(a))) * math.sqrt(float(b.dot(b)))
+    return abs(float(dot)) / den if den > 0 and math.isfinite(den) else 0.0
+
+
 class KeyedDraws:
     """Philox draws keyed by (seed, chain, t, slot); see the slot table in nuts.hip."""
 
@@ -85,7 +124,9 @@ class SequenceDraws:
 
 
 class _Nuts:
-    def __init__(self, potential_and_grad, inv_mass, step_size, draws, multinomial, dtype):
+    def __init__(self, potential_and_grad, inv_mass, step_size, draws, multinomial, dtype,
+                 margins=None):
+        self.margins = margins
         self.pg = potential_and_grad
         self.dtype = np.dtype(dtype).type
         self.v = np.asarray(inv_mass, dtype=self.dtype)
@@ -116,6 +157,13 @@ class _Nuts:
     def is_turning(self, r_left_unscaled, r_right_unscaled, r_sum):
         """nuts.py:184-195."""
         rho = r_sum - (r_left_unscaled + r_right_unscaled) / 2
+        if self.margins is not None:
+            with np.errstate(all="ignore"):
+                dots = [(float(r.dot(rho)), _cosine(r.dot(rho), r, rho))
+                        for r in (r_left_unscaled, r_right_unscaled)]
+            neg = [m for d, m in dots if d <= 0]
+            signed = [math.copysign(m, d) for d, m in dots]
+            self.margins.note("turn", max(neg) if neg else min(m for _, m in dots), *signed)
         return bool(r_left_unscaled.dot(rho) <= 0) or bool(r_right_unscaled.dot(rho) <= 0)
 
     def basetree(self, z, r, z_grads, log_slice, direction, energy_current):
@@ -125,10 +173,17 @@ class _Nuts:
         self.n_grad_evals += 1
         r_new_unscaled = self.unscale(r_new)
         energy_new = self.dtype(pe) + self.kinetic(r_new_unscaled)
+        if self.margins is not None and not math.isfinite(energy_new):
+            self.margins.nonfinite_energy += 1
+            self.margins.nan_energy += int(math.isnan(energy_new))
         if math.isnan(energy_new):
             energy_new = self.dtype(math.inf)
         sliced = energy_new + log_slice
         diverging = bool(sliced > MAX_SLICED_ENERGY)
+        if self.margins is not None:
+            self.margins.note("diverge", abs(float(sliced) - MAX_SLICED_ENERGY), sliced)
+            if not self.multinomial and not diverging:
+                self.margins.note("slice", abs(float(sliced)))
         delta = energy_new - energy_current
         with np.errstate(over="ignore"):
             accept_prob = min(float(np.exp(-delta)), 1.0)
@@ -167,6 +222,8 @@ class _Nuts:
         else:
             other_prob = other.weight / weight if weight > 0 else 0.0
         u = self.draws.merge(j, depth, offset >> depth)
+        if self.margins is not None:
+            self.margins.note("draw", abs(u - other_prob), other_prob)
         if u < other_prob:   # Bernoulli(probs).sample() == 1  <=>  rand < probs
             z_prop, z_prop_pe, z_prop_grads = other.z_proposal, other.z_proposal_pe, \
                 other.z_proposal_grads
@@ -183,9 +240,10 @@ class _Nuts:
 
 
 def nuts_transition(z, pe, z_grads, potential_and_grad, inv_mass, step_size, draws,
-                    max_tree_depth=10, multinomial=True, dtype=np.float64):
-    """nuts.py:367-522 for one chain. Returns a dict with the next state and statistics."""
-    n = _Nuts(potential_and_grad, inv_mass, step_size, draws, multinomial, dtype)
+                    max_tree_depth=10, multinomial=True, dtype=np.float64, margins=None):
+    """nuts.py:367-522 for one chain. Returns a dict with the next state and statistics.
+    ``margins``: an optional Margins() that collects how far every decision was from its threshold."""
+    n = _Nuts(potential_and_grad, inv_mass, step_size, draws, multinomial, dtype, margins)
     dt = n.dtype
     z = np.asarray(z, dtype=dt)
     z_grads = np.asarray(z_grads, dtype=dt)
@@ -209,7 +267,10 @@ def nuts_transition(z, pe, z_grads, potential_and_grad, inv_mass, step_size, dra
     pe_out = pe
     while tree_depth < max_tree_depth:
         j = tree_depth
-        direction = 1 if draws.direction(j) < 0.5 else -1    # Bernoulli(0.5).sample()
+        u_dir = draws.direction(j)
+        direction = 1 if u_dir < 0.5 else -1                 # Bernoulli(0.5).sample()
+        if margins is not None:
+            margins.note("direction", abs(u_dir - 0.5), 0.5)
         if direction == 1:
             new = n.build_tree(z_right, r_right, g_right, log_slice, direction, tree_depth,
                                energy_current, j, 0)
@@ -233,6 +294,8 @@ def nuts_transition(z, pe, z_grads, potential_and_grad, inv_mass, step_size, dra
         else:
             new_prob = new.weight / tree_weight
         rand = draws.accept(j)
+        if margins is not None:
+            margins.note("draw", abs(rand - new_prob), new_prob)
         if rand < new_prob:
             accepted = True
             z, z_grads, pe_out = new.z_proposal, new.z_proposal_grads, new.z_proposal_pe
@@ -246,3 +309,53 @@ def nuts_transition(z, pe, z_grads, potential_and_grad, inv_mass, step_size, dra
     return {"z": z, "pe": pe_out, "grad": z_grads, "accept_prob": sum_accept / num_prop,
             "n_leapfrog": num_prop, "depth": tree_depth, "diverging": diverged,
             "accepted": accepted}
+
+
+def find_step_gaussian(z, pe, grad, Lambda, inv_mass, step, seed, key, chain, min_step, max_step,
+                       threshold, dtype, draw_dtype=None, normals=None, margins=None):
+    """nuts_gaussian_find_step_kernel (pyro_amd/csrc/nuts.hip) for one chain, statement by statement
+    in ``dtype`` arithmetic, with the kernel's draws: trial ``it`` takes its momentum from
+    philox.normal(D, draw_dtype, seed, (key + it) << 20, chain) (``draw_dtype`` defaults to ``dtype``;
+    ``normals(it)`` injects other draws).  Returns (step, number of trials)."""
+    dt = np.dtype(dtype).type
+    ddt = dt if draw_dtype is None else np.dtype(draw_dtype).type
+    z, g = np.asarray(z, dtype=dt), np.asarray(grad, dtype=dt)
+    L, v = np.asarray(Lambda, dtype=dt), np.asarray(inv_mass, dtype=dt)
+    D = z.shape[0]
+    sq = np.sqrt(v)
+    isq = dt(1) / sq
+    pe, lo, hi, thr = dt(pe), dt(min_step), dt(max_step), dt(threshold)
+    trials = [0]
+
+    def trial(e, it):
+        trials[0] += 1
+        if normals is not None:
+            ru = np.asarray(normals(it), dtype=dt)
+        else:
+            ru = philox.normal(D, ddt, seed, (key + it) << 20, chain).astype(dt)
+        with np.errstate(all="ignore"):
+            r = ru * isq
+            e0 = dt(0.5) * dt(ru.dot(ru)) + pe
+            hk = dt(0.5) * e
+            r = r + hk * (-g)
+            z1 = z + e * (v * r)
+            g1 = L @ z1
+            pe1 = dt(0.5) * dt(z1.dot(g1))
+            r = r + hk * (-g1)
+            ru1 = r * sq
+            delta = (dt(0.5) * dt(ru1.dot(ru1)) + pe1) - e0
+        if margins is not None:
+            margins.note("find_step", abs(float(thr) + float(delta)), delta)
+        return 1 if thr < -delta else -1                     # NaN compares false: direction -1
+
+    eps = dt(step)
+    direction = trial(eps, 0)
+    scale = dt(2) if direction > 0 else dt(0.5)
+    for it in range(1, 201):
+        if not (eps > lo and eps < hi):
+            break
+        eps = dt(eps * scale)
+        if trial(eps, it) != direction:
+            break
+    eps = lo if eps < lo else (hi if eps > hi else eps)
+    return eps, trials[0]

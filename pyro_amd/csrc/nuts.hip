@@ -63,11 +63,18 @@ template <typename T> __device__ __forceinline__ T dot(P2<T> x, P2<T> y) {
 }
 
 // ---- potentials: g = Lambda z (Lambda symmetric, read as columns), pe = 0.5 z.g ---------------
-// PotLds: Lambda staged once per workgroup in LDS (any dtype, D <= 128).
-template <typename T>
+// PotLds: Lambda staged once per workgroup in LDS (any dtype, D <= 128).  The lanes past D read up
+// to 127 elements beyond the D*D matrix (their sums are discarded): the LDS copy is padded by 128
+// zeros for that; GUARD = true masks those loads instead, for a Lambda that is read in place from
+// global memory, where nothing says what lies behind it.
+template <typename T, bool GUARD = false>
 struct PotLds {
   const T* Ls;
   int D, lane;
+  __device__ __forceinline__ T at(int idx, bool ok) const {
+    if constexpr (GUARD) return ok ? Ls[idx] : T(0);
+    else return Ls[idx];
+  }
   // Four partial sums per column (rows j = k mod 4), combined as (s0 + s1) + (s2 + s3): four
   // independent FMA chains instead of one of length D -- with one wave per SIMD nothing else hides
   // the FMA latency.  PotReg below uses the same partition and order: bit-identical results.
@@ -77,14 +84,14 @@ struct PotLds {
 #pragma unroll 4
     for (int j = 0; j < d0; ++j) {
       const T zj = bcast_lane(z.a, j);
-      s0[j & 3] = __builtin_fma(Ls[j * D + lane], zj, s0[j & 3]);
-      s1[j & 3] = __builtin_fma(Ls[j * D + lane + 64], zj, s1[j & 3]);
+      s0[j & 3] = __builtin_fma(at(j * D + lane, lane < D), zj, s0[j & 3]);
+      s1[j & 3] = __builtin_fma(at(j * D + lane + 64, lane + 64 < D), zj, s1[j & 3]);
     }
 #pragma unroll 4
     for (int j = 64; j < D; ++j) {
       const T zj = bcast_lane(z.b, j - 64);
-      s0[j & 3] = __builtin_fma(Ls[j * D + lane], zj, s0[j & 3]);
-      s1[j & 3] = __builtin_fma(Ls[j * D + lane + 64], zj, s1[j & 3]);
+      s0[j & 3] = __builtin_fma(at(j * D + lane, lane < D), zj, s0[j & 3]);
+      s1[j & 3] = __builtin_fma(at(j * D + lane + 64, lane + 64 < D), zj, s1[j & 3]);
     }
     const T g0 = (s0[0] + s0[1]) + (s0[2] + s0[3]);
     const T g1 = (s1[0] + s1[1]) + (s1[2] + s1[3]);
@@ -512,7 +519,7 @@ __global__ __launch_bounds__(64) void nuts_gaussian_find_step_kernel(
   const P2<T> sq{Num<T>::sqrt_(v.a), Num<T>::sqrt_(v.b)};
   const P2<T> isq{T(1) / sq.a, T(1) / sq.b};
   const uint64_t cid = chain_offset + (uint64_t)chain;
-  PotLds<T> pot{Lambda, D, lane};
+  PotLds<T, true> pot{Lambda, D, lane};   // global memory: no padding behind Lambda
   T eps = step[chain];
 
   auto trial = [&](T e, uint64_t it) -> int {

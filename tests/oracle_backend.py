@@ -349,6 +349,21 @@ def nuts_gaussian_run(z, pe, grad, Lambda, inv_mass, step, max_tree_depth, use_m
     return out
 
 
+def nuts_gaussian_find_step(z, pe, grad, Lambda, inv_mass, step, seed, key, chain_offset,
+                            min_step, max_step, direction_threshold):
+    """Stand-in of pa_nuts_gaussian_find_step: oracle/nuts.find_step_gaussian per chain, in float64
+    arithmetic on the draws of the tensors' dtype; inv_mass [D] or [C, D]."""
+    C, D = z.shape
+    np_dt = np.float32 if z.dtype == torch.float32 else np.float64
+    im = _np(inv_mass if inv_mass.dim() == 2 else inv_mass.expand(C, D)).astype(np.float64)
+    zn, pen, gn, Ln = (_np(x).astype(np.float64) for x in (z, pe, grad, Lambda))
+    out = [o_nuts.find_step_gaussian(zn[c], pen[c], gn[c], Ln, im[c], float(_np(step)[c]), seed, key,
+                                     chain_offset + c, np_dt(min_step), np_dt(max_step),
+                                     np_dt(direction_threshold), np.float64, draw_dtype=np_dt)[0]
+           for c in range(C)]
+    return torch.as_tensor(np.array(out), dtype=z.dtype)
+
+
 class NutsTree:
     """Stand-in for kernels.NutsTree backed by oracle/nuts_tree.py (numpy, host)."""
 
@@ -680,7 +695,7 @@ def tall_wgrad(g, x, want_bias=True, y_mul=None):
 
 FUNCTIONS = ["bow_images_of", "bow_linear_fwd", "bow_linear_bwd", "tall_linear", "tall_wgrad", "exp_site_fwd", "exp_site_bwd", "meanfield_score", "sum_to_nd_pair", "philox_normal", "philox_uniform", "dist_log_prob", "dist_log_prob_sum",
              "dist_log_prob_grad", "glm_bernoulli_fwd_bwd", "leapfrog_kick_drift", "leapfrog_kick",
-             "nuts_gaussian_transition", "nuts_gaussian_run", "lda_factor_fwd_bwd", "adam_step", "NutsTree", "GroupSegments",
+             "nuts_gaussian_transition", "nuts_gaussian_run", "nuts_gaussian_find_step", "lda_factor_fwd_bwd", "adam_step", "NutsTree", "GroupSegments",
              "glm_bernoulli_grouped_fwd_bwd", "grouped_rows_of", "glm_grouped_rows_servable", "multi_log_prob_sum", "multi_log_prob_grad", "multi_log_prob_sum_grad",
              "meanfield_normal_sample", "meanfield_normal_sample_bwd", "glm_chain", "chain_matvec", "mvn_tril_sample",
              "mvn_tril_sample_bwd", "logchain_fwd_bwd", "dist_log_prob_sum_nd", "dist_log_prob_grad_nd", "sum_to_nd",
