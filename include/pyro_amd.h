@@ -868,6 +868,30 @@ int pa_logchain_fwd_bwd(int dtype, const void* unary, const void* pairwise,
                         int64_t T, int64_t K, void* log_z, void* grad_unary, void* grad_pairwise,
                         void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/logchain_decode.hip: the same chain decoded -- its most probable path, or one joint posterior draw -------
+ * Replaces, for infer_discrete on a model written with pyro.markov (pyro/infer/discrete.py
+ * _sample_posterior_from_trace with pyro/ops/einsum/torch_map.py, torch_sample.py): one contraction of the whole chain
+ * per state.  unary, pairwise, the strides and the limits as pa_logchain_fwd_bwd (pairwise may be NULL for T = 1).
+ * With (+) = max (mode 0) or log-sum-exp (mode 1):
+ *   backward  m_{T-1} = 0,  m_t[i] = (+)_j (pair[b,t,i,j] + unary[b,t+1,j] + m_{t+1}[j])   (kept in the workspace)
+ *   forward   s_t[j] = (t ? pair[b,t-1,z_{t-1},j] : 0) + unary[b,t,j] + m_t[j]
+ *     mode 0: z_out[b][t] = the smallest j with s_t[j] = max_j s_t[j]                       (the Viterbi path);
+ *     mode 1: z_out[b][t] = the smallest j with c_j > r c_{K-1}, clamped to the largest j with e_j > 0, where
+ *             e_j = exp(s_t[j] - max_j s_t[j]), c = the prefix sums of e in index order and r = element b of the
+ *             uniform stream (seed, offset + t * step_blocks [+ *offset_dev, for draws under a capture]) in `dtype`,
+ *             mapped from Philox blocks as pa_philox_uniform maps them: with step_blocks = ceil(B / 4) (f32) or
+ *             ceil(B / 2) (f64) step t draws what the t-th of T consecutive reservations of B uniforms holds;
+ *   log_norm[b] = (+)_j (unary[b,0,j] + m_0[j]): the score of the returned path (mode 0) or log Z (mode 1).
+ * A step whose scores are all -inf or hold a NaN gets 0, and the chain goes on from state 0.  z_out: B T int64,
+ * row-major, written by ordinary vector stores.  One launch, one wave per sequence, bit-reproducible.
+ * workspace: pa_logchain_decode_workspace(dtype, B, T, K) bytes.  B = 0: PA_OK without a launch; K > 64:
+ * PA_ERR_UNSUPPORTED. */
+size_t pa_logchain_decode_workspace(int dtype, int64_t B, int64_t T, int64_t K);
+int pa_logchain_decode(int dtype, const void* unary, const void* pairwise, int64_t pair_stride_batch,
+                       int64_t pair_stride_step, int64_t B, int64_t T, int64_t K, int mode, uint64_t seed,
+                       uint64_t offset, const uint64_t* offset_dev, uint64_t step_blocks, int64_t* z_out,
+                       void* log_norm, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -317,6 +317,10 @@ _SIGNATURES = {
     "pa_logchain_fwd_bwd": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                     c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    "pa_logchain_decode_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64]),
+    "pa_logchain_decode": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int,
+                                   c_uint64, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

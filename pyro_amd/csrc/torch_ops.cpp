@@ -380,6 +380,38 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> logchain(const at::Tensor& unary,
   return {log_z, gu, gp};
 }
 
+// the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
+// path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
+// [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
+std::tuple<at::Tensor, at::Tensor> logchain_decode(const at::Tensor& unary, const at::Tensor& pairwise, int64_t mode,
+                                                   int64_t seed, int64_t offset,
+                                                   const std::optional<at::Tensor>& offset_dev, int64_t step_blocks) {
+  const int dt = dtype_of(unary, "logchain_decode");
+  TORCH_CHECK(unary.dim() == 3 && unary.is_contiguous(), "pyro_amd::logchain_decode: unary [B, T, K] contiguous");
+  const int64_t B = unary.size(0), T = unary.size(1), K = unary.size(2);
+  int64_t sb = 0, ss = 0;
+  const void* pp = nullptr;
+  if (T > 1) {
+    TORCH_CHECK(pairwise.is_contiguous() && pairwise.scalar_type() == unary.scalar_type() && pairwise.dim() == 4 &&
+                    pairwise.size(2) == K && pairwise.size(3) == K && (pairwise.size(0) == B || pairwise.size(0) == 1) &&
+                    (pairwise.size(1) == T - 1 || pairwise.size(1) == 1),
+                "pyro_amd::logchain_decode: pairwise [B | 1, T - 1 | 1, K, K] contiguous, of unary's dtype");
+    sb = pairwise.size(0) == 1 ? 0 : pairwise.stride(0);
+    ss = pairwise.size(1) == 1 ? 0 : pairwise.stride(1);
+    pp = pairwise.data_ptr();
+  }
+  const size_t ws_bytes = pa_logchain_decode_workspace(dt, B, T, K);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, unary.options().dtype(at::kByte));
+  at::Tensor z = at::empty({B, T}, unary.options().dtype(at::kLong)), log_norm = at::empty({B}, unary.options());
+  const uint64_t* od = nullptr;
+  if (offset_dev.has_value() && offset_dev->defined()) od = (const uint64_t*)offset_dev->data_ptr();
+  check(pa_logchain_decode(dt, unary.data_ptr(), pp, sb, ss, B, T, K, (int)mode, (uint64_t)seed, (uint64_t)offset, od,
+                           (uint64_t)step_blocks, (int64_t*)z.data_ptr(), log_norm.data_ptr(), ws.data_ptr(), ws_bytes,
+                           current_stream()),
+        "logchain_decode");
+  return {z, log_norm};
+}
+
 // the leaf of a plated mixture under TraceEnum_ELBO / the enumerated potential of HMC and NUTS: the observed site's
 // log_prob against every value of the enumerated assignment (pyro/poutine/trace_struct.py:248-288), logsumexp over it
 // (pyro/ops/contract.py:79-160) and the plate sum, forward and backward in one pass over the data, for B parameter
@@ -520,6 +552,8 @@ TORCH_LIBRARY(pyro_amd, m) {
         "(Tensor eps, Tensor z, Tensor logq)");
   m.def("logsumexp_terms(Tensor[] terms, int[] sizes, int rdim) -> Tensor");
   m.def("logchain(Tensor unary, Tensor pairwise) -> (Tensor log_z, Tensor grad_unary, Tensor grad_pairwise)");
+  m.def("logchain_decode(Tensor unary, Tensor pairwise, int mode, int seed, int offset, Tensor? offset_dev, "
+        "int step_blocks) -> (Tensor z, Tensor log_norm)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -547,6 +581,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("mvn_tril_sample", &mvn_tril_sample);
   m.impl("logsumexp_terms", &logsumexp_terms);
   m.impl("logchain", &logchain);
+  m.impl("logchain_decode", &logchain_decode);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

@@ -16,8 +16,21 @@ Two routes, site by site in the order the model visits them:
     features through ``.to_event(1)`` and a full-covariance MultivariateNormal over at most 64; an outer plate of
     parameter sets is optional): kernels.mixture_assign* picks or draws every row's component in one pass, and
     nothing of size K N (let alone K N D) exists beyond the caller's own per-row weights.
-    ``ops.contract.FUSED_MIXTURE = False`` turns it off.
-Both routes draw from the same uniforms in the same way, so at a fixed seed they return the same values.
+    ``ops.contract.FUSED_MIXTURE = False`` turns it off;
+  * fast -- a ``pyro.markov`` chain: the sites of one component of the enumerated factor graph form a simple path in
+    the order the model declares them, none of them fixed yet, all in one plate context (factors under deeper plates --
+    observations in a plate nested inside -- are product-reduced to it first), at most 64 states, float32 / float64 on
+    the device.  When the chain's first site is asked for, kernels.logchain_decode fixes all T of them in ONE launch
+    -- backward max / log-sum-exp messages, then every state given the one before: the Viterbi path at temperature 0,
+    a joint posterior draw at temperature 1 -- in O(T K^2) per sequence with a [B, T, K] workspace, where the generic
+    route contracts the whole chain once per site; the later sites read the kept values.  The T steps' uniforms are
+    reserved in one go as T reservations of one uniform per sequence would be.  Anything else -- a tree, a site shared
+    by two chains, more than 64 states, a chain with a state already fixed or conditioned -- stays on the generic
+    route.  ``ops.contract.FUSED_CHAIN = False`` turns it off.
+Both routes draw from the same uniforms in the same way, so at a fixed seed they return the same values -- for a chain
+as long as no other drawing site is visited between the chain's sites: the generic route reserves a site's uniforms
+when it visits the site, the chain route all T sites' at the first; with sites interleaved the result is still one
+joint posterior draw, from other uniforms.
 """
 import functools
 import warnings
@@ -27,14 +40,20 @@ import torch
 from .. import kernels, poutine, rng
 from ..ops import contract
 from ..poutine.util import prune_subsample_sites
-from .traceenum_elbo import (BackwardSample, _enum_log_prob, _enum_sites, _evidence_of, _lazy_family, _ordinal,
-                             _packed, _posterior_of, _posterior_weights, _support_last)
+from .traceenum_elbo import (BackwardSample, _enum_factors, _enum_log_prob, _enum_sites, _evidence_of, _lazy_family,
+                             _ordinal, _packed, _posterior_of, _posterior_weights, _support_last)
 
 
 def _wide_assign_ready(x):
     """Whether the wide leaves' assignment kernels (kernels.mixture_assign_event / mixture_assign_mvn) can take the
     observation ``x``: they run on the device only."""
     return x.is_cuda
+
+
+def _chain_decode_ready(t):
+    """Whether the chain decoding kernel (kernels.logchain_decode) can take the potentials ``t``: it runs on the
+    device only."""
+    return t.is_cuda
 
 
 def _uniform(shape, dtype, device, on_device):
@@ -101,11 +120,16 @@ class _InferDiscrete(BackwardSample):
         super().__init__(model_trace, enum_names, enum_ids)
         self.temperature = temperature
         self._fixed = {}                  # values set so far whose evidence tensors nobody has asked for yet
+        self._decoded = {}                # support indices of a chain's sites, kept from its one launch
 
     def _choose(self, msg):
         name = msg["name"]
         site = self.model_trace.nodes[name]
-        index = self._fast(name, site)
+        index = self._decoded.pop(name, None)
+        if index is None:
+            index = self._fast(name, site)
+        if index is None:
+            index = self._decode(name, site)
         if index is None:
             index = self._generic(name)
         msg["value"] = _value_of(site["fn"], index, site["value"])
@@ -128,6 +152,60 @@ class _InferDiscrete(BackwardSample):
         probs = _posterior_of(*args).detach()
         u = _uniform(probs.shape[:-1], probs.dtype, probs.device, kernels.on_device(probs))
         return inverse_cdf(probs, u)
+
+    def _decode(self, name, site):
+        """The site's support indices from kernels.logchain_decode when the site is the first of a pyro.markov chain
+        the kernel takes (the other sites' indices are kept for their turn), else None."""
+        if not contract.FUSED_CHAIN or name in self.evidence or name in self._fixed:
+            return None
+        trace = self.model_trace
+        name_of = {trace.nodes[n]["infer"]["_dim_to_id"][trace.nodes[n]["infer"]["_enumerate_dim"]]: n
+                   for n in self.enum_names}
+        kid = site["infer"]["_dim_to_id"][site["infer"]["_enumerate_dim"]]
+        factors = _enum_factors(trace, self.enum_names, self.enum_ids, {})
+        every = [t for terms in factors.values() for t in terms]
+        found = [(terms, ids) for terms, ids in contract._partition(every, set(self.enum_ids)) if kid in ids]
+        if len(found) != 1:
+            return None
+        terms, ids = found[0]
+        ordinal = _ordinal(site)
+        if len(ids) < 3 or any(v not in name_of or name_of[v] in self.evidence or name_of[v] in self._fixed
+                               or _ordinal(trace.nodes[name_of[v]]) != ordinal for v in ids):
+            return None                       # (a state already fixed, or sites in different plate contexts)
+        reduced = []
+        for t in terms:
+            if not set(t.ids) <= ids or not t.ordinal >= ordinal:
+                return None
+            # factors below the chain's plates (observations in a plate nested inside): their plate product first
+            tensor = contract._product(t.dense(), t.ordinal - ordinal) if t.ordinal != ordinal else t.dense()
+            reduced.append(contract.Term(tensor.detach(), t.ids, ordinal))
+        match = contract._match_chain(reduced, ids, ready=_chain_decode_ready)
+        if match is None:
+            return None
+        order, U, P, batch = match
+        declared = [n for n in trace.nodes if n in self.enum_names and n in {name_of[v] for v in ids}]
+        along = [name_of[v] for v in order]
+        if along == declared[::-1]:           # the path was walked from its other end
+            U, P = U.flip(1).contiguous(), P.flip(1).transpose(-1, -2).contiguous()
+        elif along != declared:
+            return None
+        if declared[0] != name:
+            return None
+        B, T, _ = U.shape
+        if self.temperature == 1:
+            per = 4 if U.dtype == torch.float32 else 2    # uniforms per Philox block: rng.reserve's rule
+            blocks = (B + per - 1) // per
+            seed, off, off_dev = rng.reserve_blocks(T * blocks)
+        else:
+            blocks, seed, off, off_dev = 0, 0, 0, None
+        z, _ = kernels.logchain_decode(U, P, mode=self.temperature, seed=seed, offset=off, offset_dev=off_dev,
+                                       step_blocks=blocks)
+        shape = tuple(batch)
+        while shape and shape[0] == 1:        # (as _support_last shapes the generic route's indices)
+            shape = shape[1:]
+        for t, n in enumerate(declared):
+            self._decoded[n] = z[:, t].reshape(shape)
+        return self._decoded.pop(name)
 
     def _fast(self, name, site):
         """The site's support indices from kernels.mixture_assign*, shaped like the site's plates, or None when the

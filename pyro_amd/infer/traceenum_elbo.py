@@ -653,9 +653,10 @@ def _enum_sites(model_trace, guide_trace):
     return names, ids
 
 
-def _log_partition(model_trace, enum_names, enum_ids, extra):
-    """log Z of the enumerated part of the model: every factor that carries an enumerated name,
-    summed out over names and plates.  ``extra[name]`` is added to site ``name``'s factor."""
+def _enum_factors(model_trace, enum_names, enum_ids, extra):
+    """{ordinal: [Term]}: every factor of the model that carries an enumerated name -- the enumerated sites' own
+    (unmasked) and the masked log-probabilities of the sites that depend on them.  ``extra[name]`` is added to site
+    ``name``'s factor."""
     first_enum_dim = model_trace._first_enum_dim
     factors = OrderedDict()
     for name, site in model_trace.nodes.items():
@@ -674,6 +675,13 @@ def _log_partition(model_trace, enum_names, enum_ids, extra):
         term = _packed(site, scale_and_mask(lp, mask=site["mask"]), first_enum_dim)
         if term.dims & enum_ids:
             factors.setdefault(term.ordinal, []).append(term)
+    return factors
+
+
+def _log_partition(model_trace, enum_names, enum_ids, extra):
+    """log Z of the enumerated part of the model: every factor that carries an enumerated name,
+    summed out over names and plates.  ``extra[name]`` is added to site ``name``'s factor."""
+    factors = _enum_factors(model_trace, enum_names, enum_ids, extra)
     total = 0.0
     for ordinal, terms in contract_tensor_tree(factors, enum_ids, reduce_all=True).items():
         for term in terms:

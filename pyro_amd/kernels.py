@@ -756,8 +756,24 @@ def logchain_fwd_bwd(unary, pairwise):
     (log_z [B], grad_unary [B, T, K], grad_pairwise [B, T-1, K, K])."""
     _require_gpu(unary, pairwise)
     B, T, K = unary.shape
-    assert unary.is_contiguous() and (T == 1 or pairwise.is_contiguous())
+    spb, spt = _chain_pair_strides(unary, pairwise)
     lib = _lib.load()
+    log_z = torch.empty((B,), dtype=unary.dtype, device=unary.device)
+    g_u = torch.empty_like(unary)
+    g_p = torch.empty((B, max(T - 1, 0), K, K), dtype=unary.dtype, device=unary.device)
+    nbytes = lib.pa_logchain_workspace(_dtype(unary), B, T, K)
+    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=unary.device)
+    check(lib.pa_logchain_fwd_bwd(_dtype(unary), _ptr(unary), _ptr(pairwise) if T > 1 else None,
+                                  spb, spt, B, T, K, _ptr(log_z), _ptr(g_u), _ptr(g_p), _ptr(ws),
+                                  nbytes, _stream()))
+    return log_z, g_u, g_p
+
+
+def _chain_pair_strides(unary, pairwise):
+    """The argument checks the chain kernels share: unary [B, T, K] contiguous, pairwise [B, T-1, K, K] / [T-1, K, K] /
+    [K, K] contiguous (not looked at for T = 1) -> (pair_stride_batch, pair_stride_step)."""
+    B, T, K = unary.shape
+    assert unary.is_contiguous() and (T == 1 or pairwise.is_contiguous())
     spb = spt = 0
     if T > 1:
         assert pairwise.dtype == unary.dtype and pairwise.shape[-2:] == (K, K)
@@ -769,15 +785,30 @@ def logchain_fwd_bwd(unary, pairwise):
             spt = K * K
         else:
             assert pairwise.dim() == 2
-    log_z = torch.empty((B,), dtype=unary.dtype, device=unary.device)
-    g_u = torch.empty_like(unary)
-    g_p = torch.empty((B, max(T - 1, 0), K, K), dtype=unary.dtype, device=unary.device)
-    nbytes = lib.pa_logchain_workspace(_dtype(unary), B, T, K)
+    return spb, spt
+
+
+def logchain_decode(unary, pairwise, mode=0, seed=0, offset=0, offset_dev=None, step_blocks=0):
+    """A chain of enumerated variables decoded in ONE launch (pa_logchain_decode): unary [B, T, K], pairwise as for
+    logchain_fwd_bwd (None allowed for T = 1).  ``mode`` 0: the most probable path (Viterbi: backward max messages,
+    then the first argmax of every step given the step before); ``mode`` 1: one joint draw from the chain's posterior
+    (backward log-sum-exp messages, then every step by inverse CDF on element b of the Philox uniform stream (seed,
+    offset + t * step_blocks[, offset_dev]) in unary's dtype -- with step_blocks = ceil(B / 4) (float32) or
+    ceil(B / 2) (float64) the uniforms of T consecutive ``rng.reserve(B, dtype)``).
+    -> (z int64 [B, T], log_norm [B]: the path's score (mode 0) or log Z (mode 1)); a step with no finite score gets
+    0.  K > 64 raises Unsupported."""
+    _require_gpu(unary, pairwise, offset_dev)
+    B, T, K = unary.shape
+    spb, spt = _chain_pair_strides(unary, pairwise)
+    lib = _lib.load()
+    z = torch.empty((B, T), dtype=torch.int64, device=unary.device)
+    log_norm = torch.empty((B,), dtype=unary.dtype, device=unary.device)
+    nbytes = lib.pa_logchain_decode_workspace(_dtype(unary), B, T, K)
     ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=unary.device)
-    check(lib.pa_logchain_fwd_bwd(_dtype(unary), _ptr(unary), _ptr(pairwise) if T > 1 else None,
-                                  spb, spt, B, T, K, _ptr(log_z), _ptr(g_u), _ptr(g_p), _ptr(ws),
-                                  nbytes, _stream()))
-    return log_z, g_u, g_p
+    check(lib.pa_logchain_decode(_dtype(unary), _ptr(unary), _ptr(pairwise) if T > 1 else None, spb, spt, B, T, K,
+                                 int(mode), int(seed), int(offset), _ptr(offset_dev), int(step_blocks), _ptr(z),
+                                 _ptr(log_norm), _ptr(ws), nbytes, _stream()))
+    return z, log_norm
 
 
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):

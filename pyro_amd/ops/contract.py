@@ -25,7 +25,7 @@ from .. import kernels
 from .torch_library import dispatcher_op as _dispatcher_op
 
 
-FUSED_CHAIN = True            # HMM-shaped components go through pa_logchain_fwd_bwd
+FUSED_CHAIN = True            # HMM-shaped components go through pa_logchain_fwd_bwd (infer_discrete: _decode)
 
 
 class Term:
@@ -502,10 +502,13 @@ class _LogChain(torch.autograd.Function):
         return g.reshape(-1, 1, 1) * g_u, d_pair
 
 
-def _try_fused_chain(terms, sum_ids):
-    """A component whose names form a simple path (every term mentions one or two of them, the
-    two-name terms link consecutive variables: an HMM written with pyro.markov) is summed out by
-    the fused forward-backward kernel.  Returns the packed tensor [*plate block] or None."""
+def _match_chain(terms, sum_ids, ready=None):
+    """The pattern of the chain kernels: a component whose names form a simple path (every term mentions one or two
+    of them, the two-name terms link consecutive variables: an HMM written with pyro.markov), at most 64 states, one
+    plate block.  ``ready``: whether the kernels can take a tensor (kernels.on_device unless given).
+    -> (order: the names along the path, U [B, T, K], P [B, T-1, K, K] (P[b, t, i, j]: order[t] = i, order[t+1] = j),
+    batch: the plate block's shape, B its size) or None.  Shared by the contraction (_try_fused_chain) and by
+    infer_discrete (infer/discrete.py)."""
     T = len(sum_ids)
     if T < 3 or not terms:
         return None
@@ -515,7 +518,7 @@ def _try_fused_chain(terms, sum_ids):
             return None
         proto = t.tensor if proto is None else proto
     if proto.dtype not in (torch.float32, torch.float64) or \
-            not kernels.on_device(proto):
+            not (kernels.on_device if ready is None else ready)(proto):
         return None
     adj = {v: set() for v in sum_ids}
     for t in terms:
@@ -574,7 +577,17 @@ def _try_fused_chain(terms, sum_ids):
     nb = len(batch)
     U = U.permute(tuple(range(2, 2 + nb)) + (0, 1)).reshape(B, T, K).contiguous()
     P = P.permute(tuple(range(3, 3 + nb)) + (0, 1, 2)).reshape(B, T - 1, K, K).contiguous()
-    return _LogChain.invoke(U, P).reshape(tuple(batch))
+    return order, U, P, tuple(batch)
+
+
+def _try_fused_chain(terms, sum_ids):
+    """A component the chain pattern matches (_match_chain) is summed out by the fused forward-backward kernel.
+    Returns the packed tensor [*plate block] or None."""
+    match = _match_chain(terms, sum_ids)
+    if match is None:
+        return None
+    _, U, P, batch = match
+    return _LogChain.invoke(U, P).reshape(batch)
 
 
 FUSED_SUMPRODUCT = True       # eliminations go through pa_logsumexp_terms (one pass, no frame tensor)
