@@ -892,6 +892,43 @@ int pa_logchain_decode(int dtype, const void* unary, const void* pairwise, int64
                        uint64_t offset, const uint64_t* offset_dev, uint64_t step_blocks, int64_t* z_out,
                        void* log_norm, void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gaussian_hmm.hip: a linear-Gaussian state-space model -- Kalman filter and smoother gradients ------------
+ * Replaces GaussianHMM.log_prob / .filter (pyro/distributions/hmm.py:434-741 over sequential_gaussian_tensordot,
+ * pyro/ops/gaussian.py: O(log T) rounds of batched Gaussian contractions and their autograd duals) with one launch,
+ * one wave per sequence.  Row vectors, as the reference writes the model:
+ *   z_0 ~ N(m0, P0),   z_t = z_{t-1} F_t + N(q_t, Q_t),   x_t = z_t H_t + N(r_t, R_t),   t = 1..T
+ * F [hidden(old), hidden(new)], H [hidden, obs], covariances symmetric positive definite, all row-major.
+ * Parameter p of sequence b at step t is read at p + b * p_stride_batch + t * p_stride_step (elements; 0 = shared
+ * by the sequences / time-homogeneous; m0 and P0 have no step).  x [B, T, obs] contiguous.
+ *   log_prob[b]       = log p(x[b, 1..T])
+ *   filter_mean / filter_cov (both or neither; may be NULL): the filtered moments of z_T, [B, hidden], [B, hidden, hidden]
+ *   grad_* (all nine or none): d log_prob[b] / d input, contiguous [B, ...] for m0 and P0, [B, T, obs] for x,
+ *     [B, T, ...] for a parameter with a step stride and [B, ...] (summed over the steps inside the kernel, in the
+ *     fixed order of the backward sweep) for one without; the sum over sequences of a batch-shared parameter is
+ *     the caller's.  Covariance gradients are the symmetric dL/dSigma.  With zbar, Ps the smoothed moments,
+ *     C_t = Cov(z_{t-1}, z_t | x), ebar_t = zbar_t - zbar_{t-1} F_t - q_t, ubar_t = x_t - zbar_t H_t - r_t:
+ *       d/dm0 = P0^-1 (zbar_0 - m0)           d/dP0 = P0^-1 (Ps_0 + (zbar_0 - m0)(zbar_0 - m0)^T - P0) P0^-1 / 2
+ *       d/dq  = Q^-1 ebar                      d/dQ  = Q^-1 (E - Q) Q^-1 / 2,
+ *                                               E = Ps_t - F^T C - C^T F + F^T Ps_{t-1} F + ebar ebar^T
+ *       d/dF  = (C - Ps_{t-1} F + zbar_{t-1} ebar^T) Q^-1
+ *       d/dr  = R^-1 ubar = -d/dx              d/dR  = R^-1 (H^T Ps_t H + ubar ubar^T - R) R^-1 / 2
+ *       d/dH  = (-Ps_t H + zbar_t ubar^T) R^-1
+ * A sequence whose innovation covariance has a non-positive pivot gets NaN for log_prob, the filter outputs and
+ * every gradient (the gradients also on such a pivot of P^p, Q, R or P0); other sequences are untouched.  No
+ * atomics: bit-reproducible.  hidden or obs > 16: PA_ERR_UNSUPPORTED.  B = 0: PA_OK without a launch.
+ * workspace: pa_gaussian_hmm_workspace(...) bytes -- B T (hidden + hidden^2) elements with gradients, 0 without. */
+size_t pa_gaussian_hmm_workspace(int dtype, int64_t B, int64_t T, int64_t hidden, int64_t obs, int need_grads);
+int pa_gaussian_hmm_fwd_bwd(int dtype, const void* m0, int64_t m0_stride_batch, const void* P0,
+                            int64_t P0_stride_batch, const void* F, int64_t F_stride_batch, int64_t F_stride_step,
+                            const void* q, int64_t q_stride_batch, int64_t q_stride_step, const void* Q,
+                            int64_t Q_stride_batch, int64_t Q_stride_step, const void* H, int64_t H_stride_batch,
+                            int64_t H_stride_step, const void* r, int64_t r_stride_batch, int64_t r_stride_step,
+                            const void* R, int64_t R_stride_batch, int64_t R_stride_step, const void* x, int64_t B,
+                            int64_t T, int64_t hidden, int64_t obs, void* log_prob, void* filter_mean,
+                            void* filter_cov, void* grad_m0, void* grad_P0, void* grad_F, void* grad_q, void* grad_Q,
+                            void* grad_H, void* grad_r, void* grad_R, void* grad_x, void* workspace,
+                            size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -380,6 +380,59 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> logchain(const at::Tensor& unary,
   return {log_z, gu, gp};
 }
 
+// a linear-Gaussian state-space model filtered and (with need_grads) smoothed in one launch: log p(x) per sequence, the
+// filtered moments of the final state and the nine gradients of log_prob[b] (pyro/distributions/hmm.py:434-741
+// GaussianHMM.log_prob / .filter over pyro/ops/gaussian.py sequential_gaussian_tensordot).  Layouts as
+// kernels.gaussian_hmm_fwd_bwd: m0 [B | 1, h], P0 [B | 1, h, h], the six others [B | 1, T | 1, ...], x [B, T, o];
+// grads: empty without need_grads, else in the order of the arguments (a step axis of 1 is already summed, a batch
+// axis that the parameter shares is not)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian_hmm(
+    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
+    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov,
+    const at::Tensor& x, bool need_grads) {
+  const int dt = dtype_of(x, "gaussian_hmm");
+  TORCH_CHECK(x.dim() == 3 && x.is_contiguous() && m0.dim() == 2, "pyro_amd::gaussian_hmm: x [B, T, obs] contiguous, m0 [B | 1, hidden]");
+  const int64_t B = x.size(0), T = x.size(1), o = x.size(2), h = m0.size(1);
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const std::vector<int64_t> ev[8] = {{h}, {h, h}, {h, h}, {h}, {h, h}, {h, o}, {o}, {o, o}};
+  int64_t sb[8], ss[8], steps[8];
+  for (int i = 0; i < 8; ++i) {
+    const at::Tensor& t = *p[i];
+    const int64_t lead = i < 2 ? 1 : 2, nd = lead + (int64_t)ev[i].size();
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == x.scalar_type() && t.is_contiguous() && t.dim() == nd,
+                "pyro_amd::gaussian_hmm: parameter ", i, ": a contiguous tensor of x's dtype with ", nd, " dims");
+    int64_t n = 1;
+    for (size_t d = 0; d < ev[i].size(); ++d) {
+      TORCH_CHECK(t.size(lead + (int64_t)d) == ev[i][d], "pyro_amd::gaussian_hmm: parameter ", i, " has a wrong event shape");
+      n *= ev[i][d];
+    }
+    TORCH_CHECK((t.size(0) == 1 || t.size(0) == B) && (i < 2 || t.size(1) == 1 || t.size(1) == T),
+                "pyro_amd::gaussian_hmm: parameter ", i, ": leading dims [B | 1, T | 1]");
+    steps[i] = i < 2 ? 1 : t.size(1);
+    sb[i] = t.size(0) == 1 ? 0 : steps[i] * n;
+    ss[i] = steps[i] == 1 ? 0 : n;
+  }
+  const auto opt = x.options();
+  at::Tensor log_prob = at::empty({B}, opt), fm = at::empty({B, h}, opt), fP = at::empty({B, h, h}, opt);
+  std::vector<at::Tensor> g;
+  if (need_grads) {
+    g = {at::empty({B, h}, opt), at::empty({B, h, h}, opt), at::empty({B, steps[2], h, h}, opt),
+         at::empty({B, steps[3], h}, opt), at::empty({B, steps[4], h, h}, opt), at::empty({B, steps[5], h, o}, opt),
+         at::empty({B, steps[6], o}, opt), at::empty({B, steps[7], o, o}, opt), at::empty({B, T, o}, opt)};
+  }
+  auto gp = [&](int i) { return need_grads ? g[i].data_ptr() : nullptr; };
+  const size_t ws_bytes = pa_gaussian_hmm_workspace(dt, B, T, h, o, need_grads ? 1 : 0);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, opt.dtype(at::kByte));
+  check(pa_gaussian_hmm_fwd_bwd(dt, m0.data_ptr(), sb[0], P0.data_ptr(), sb[1], trans.data_ptr(), sb[2], ss[2],
+                                trans_loc.data_ptr(), sb[3], ss[3], trans_cov.data_ptr(), sb[4], ss[4], obs.data_ptr(),
+                                sb[5], ss[5], obs_loc.data_ptr(), sb[6], ss[6], obs_cov.data_ptr(), sb[7], ss[7],
+                                x.data_ptr(), B, T, h, o, log_prob.data_ptr(), fm.data_ptr(), fP.data_ptr(), gp(0), gp(1),
+                                gp(2), gp(3), gp(4), gp(5), gp(6), gp(7), gp(8), ws.data_ptr(), ws_bytes,
+                                current_stream()),
+        "gaussian_hmm");
+  return {log_prob, fm, fP, g};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -554,6 +607,9 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("logchain(Tensor unary, Tensor pairwise) -> (Tensor log_z, Tensor grad_unary, Tensor grad_pairwise)");
   m.def("logchain_decode(Tensor unary, Tensor pairwise, int mode, int seed, int offset, Tensor? offset_dev, "
         "int step_blocks) -> (Tensor z, Tensor log_norm)");
+  m.def("gaussian_hmm(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
+        "Tensor obs_loc, Tensor obs_cov, Tensor x, bool need_grads) -> (Tensor log_prob, Tensor filter_mean, "
+        "Tensor filter_cov, Tensor[] grads)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -582,6 +638,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("logsumexp_terms", &logsumexp_terms);
   m.impl("logchain", &logchain);
   m.impl("logchain_decode", &logchain_decode);
+  m.impl("gaussian_hmm", &gaussian_hmm);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

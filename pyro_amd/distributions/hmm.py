@@ -1,5 +1,7 @@
-"""DiscreteHMM: hidden Markov model with discrete latent state and arbitrary observation
-distribution, time included in the event shape (reference: pyro/distributions/hmm.py:243-420).
+"""Hidden Markov models with time included in the event shape.
+
+DiscreteHMM: discrete latent state and arbitrary observation distribution (reference:
+pyro/distributions/hmm.py:243-420).
 
 The reference eliminates the time axis with a parallel-scan of log-space matrix products
 (_sequential_logmatmulexp, O(log T) steps of [K, K] x [K, K] products and their autograd duals).
@@ -7,7 +9,16 @@ Here log_prob is ONE launch of the forward-backward kernel (pa_logchain_fwd_bwd)
 is variable 0 of a chain of T + 1 variables, step t contributes the transition as the pairwise
 potential and the observation log-likelihood as the unary potential of variable t + 1; the launch
 returns the log-likelihood of every batch element and, as its gradient, the posterior marginals.
+
+GaussianHMM: linear-Gaussian state-space model (reference: pyro/distributions/hmm.py:434-741).  The reference
+eliminates time with sequential_gaussian_tensordot (O(log T) rounds of batched Gaussian contractions); here
+log_prob is ONE launch of the Kalman filter / Rauch-Tung-Striebel kernel (pa_gaussian_hmm_fwd_bwd), whose
+smoother pass hands back the gradient with respect to every parameter and the data.  Whatever the kernel does
+not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
+the plain-torch sequential filter of this file, differentiated by autograd.
 """
+import math
+
 import torch
 
 from torch.distributions import constraints
@@ -62,9 +73,9 @@ class DiscreteHMM(TorchDistribution):
     def _validate_sample(self, value):
         pass        # time may be longer than event_shape[0] for time-homogeneous parameters
 
-    def log_prob(self, value):
+    def _potentials(self, value):
+        """(obs_logits [..., T, K], transition logits [..., T | 1, K, K], initial logits, batch shape) of ``value``."""
         from .. import kernels
-        from ..ops.contract import _LogChain
         obs = self.observation_dist
         value = value.unsqueeze(-1 - len(obs.event_shape))
         obs_logits = obs.log_prob(value)                              # [..., T, K]
@@ -79,15 +90,23 @@ class DiscreteHMM(TorchDistribution):
         if not kernels.on_device(obs_logits):
             raise RuntimeError("pyro_amd: DiscreteHMM.log_prob needs device tensors (there is no "
                                "CPU implementation in this package)")
-        fused = K <= 64 and obs_logits.dtype in (torch.float32, torch.float64)
-        if not fused:
-            # more than 64 states (or a dtype the kernel does not take): the forward recursion
-            # step by step with device tensor ops
-            a = init
-            for t in range(T):
-                tr = trans[..., t if trans.shape[-3] > 1 else 0, :, :]
-                a = torch.logsumexp(a.unsqueeze(-1) + tr, dim=-2) + obs_logits[..., t, :]
-            return torch.logsumexp(a, dim=-1)
+        return obs_logits, trans, init, batch
+
+    @staticmethod
+    def _forward_recursion(obs_logits, trans, init):
+        """More than 64 states (or a dtype the kernel does not take): the forward recursion step by step with
+        device tensor ops -> the unnormalised log filtering distribution of the last state."""
+        a = init
+        for t in range(obs_logits.shape[-2]):
+            tr = trans[..., t if trans.shape[-3] > 1 else 0, :, :]
+            a = torch.logsumexp(a.unsqueeze(-1) + tr, dim=-2) + obs_logits[..., t, :]
+        return a
+
+    @staticmethod
+    def _chain_inputs(obs_logits, trans, init, batch):
+        """The potentials as the chain kernels take them: unary [B, T + 1, K], pairwise [B, T, K, K] / [T, K, K] /
+        [K, K]."""
+        T, K = obs_logits.shape[-2:]
         B = 1
         for n in batch:
             B *= int(n)
@@ -99,7 +118,273 @@ class DiscreteHMM(TorchDistribution):
             pair = pair[0].contiguous() if pair.shape[0] == 1 else pair.contiguous()
         else:
             pair = trans.expand(batch + (T, K, K)).reshape(B, T, K, K).contiguous()
+        return unary, pair
+
+    def log_prob(self, value):
+        from ..ops.contract import _LogChain
+        obs_logits, trans, init, batch = self._potentials(value)
+        K = obs_logits.shape[-1]
+        fused = K <= 64 and obs_logits.dtype in (torch.float32, torch.float64)
+        if not fused:
+            return torch.logsumexp(self._forward_recursion(obs_logits, trans, init), dim=-1)
+        unary, pair = self._chain_inputs(obs_logits, trans, init, batch)
         return _LogChain.invoke(unary, pair).reshape(batch)
+
+    def filter(self, value):
+        """The posterior over the final state given the observations ``value``, a ``Categorical`` of batch shape
+        ``batch_shape`` (reference: hmm.py:373-394).  It costs nothing new: the chain kernel's gradient with respect
+        to the last unary potential IS that posterior.  Detached from the parameters."""
+        from .. import kernels
+        from . import Categorical
+        with torch.no_grad():
+            obs_logits, trans, init, batch = self._potentials(value)
+            K = obs_logits.shape[-1]
+            if K <= 64 and obs_logits.dtype in (torch.float32, torch.float64):
+                unary, pair = self._chain_inputs(obs_logits, trans, init, batch)
+                _, g_u, _ = kernels.logchain_fwd_bwd(unary, pair)
+                return Categorical(probs=g_u[:, -1, :].reshape(batch + (K,)), validate_args=self._validate_args)
+            a = self._forward_recursion(obs_logits, trans, init)
+            return Categorical(logits=a.expand(batch + (K,)), validate_args=self._validate_args)
 
     def sample(self, sample_shape=torch.Size()):
         raise NotImplementedError("DiscreteHMM.sample is not built in this backend (log_prob only)")
+
+
+# ---- GaussianHMM -------------------------------------------------------------------------------------------------
+FUSED_GAUSSIAN_HMM = True     # device tensors within the kernel's limits go through pa_gaussian_hmm_fwd_bwd
+
+
+def _loc_cov(dist, what):
+    """(loc, covariance) of a MultivariateNormal or an Independent(Normal, 1), formed differentiably from the
+    tensors the caller parametrised it with."""
+    td = torch.distributions
+    if isinstance(dist, td.MultivariateNormal):
+        if "covariance_matrix" in dist.__dict__:
+            return dist.loc, dist.covariance_matrix
+        # (from precision_matrix: torch forms it differentiably; only the lower triangle counts, as for torch)
+        L = dist._unbroadcasted_scale_tril.tril()
+        cov = L @ L.transpose(-1, -2)
+        return dist.loc, cov.expand(dist.batch_shape + cov.shape[-2:])
+    if (isinstance(dist, td.Independent) and dist.reinterpreted_batch_ndims == 1
+            and isinstance(dist.base_dist, td.Normal)):
+        base = dist.base_dist
+        return base.loc, torch.diag_embed(base.scale * base.scale)
+    raise ValueError("{} must be a MultivariateNormal or an Independent(Normal, 1), got {}".format(
+        what, type(dist).__name__))
+
+
+def _step(p, t, nd):
+    """Step ``t`` of a parameter whose time axis sits ``nd`` dims from the right (size 1: time-homogeneous)."""
+    return p.select(-nd - 1, t if p.shape[-nd - 1] > 1 else 0)
+
+
+def _kalman_filter(m0, P0, F, q, Q, H, r, R, x):
+    """The sequential filter in plain torch ops: parameters broadcastable to [..., T | 1, ...] (m0, P0 without the
+    time axis), x [..., T, obs] -> (log_prob [...], filtered mean and covariance of the last state).  The same
+    arithmetic as csrc/gaussian_hmm.hip: P^p symmetrised, S = L L^T, U = P^p H L^-T, P = P^p - U U^T.  A step
+    whose S is not positive definite makes the element NaN."""
+    T, o = x.shape[-2:]
+    m, P = m0, P0
+    lp, bad = 0.0, False
+    for t in range(T):
+        Ft, qt, Qt = _step(F, t, 2), _step(q, t, 1), _step(Q, t, 2)
+        Ht, rt, Rt = _step(H, t, 2), _step(r, t, 1), _step(R, t, 2)
+        mp = (m.unsqueeze(-2) @ Ft).squeeze(-2) + qt
+        Pp = Ft.transpose(-1, -2) @ P @ Ft + Qt
+        Pp = 0.5 * (Pp + Pp.transpose(-1, -2))
+        y = x[..., t, :] - (mp.unsqueeze(-2) @ Ht).squeeze(-2) - rt
+        PH = Pp @ Ht
+        S = Ht.transpose(-1, -2) @ PH + Rt
+        L, info = torch.linalg.cholesky_ex(S)
+        bad = (info > 0) | bad
+        batch = torch.broadcast_shapes(L.shape[:-2], y.shape[:-1], PH.shape[:-2])
+        L = L.expand(batch + L.shape[-2:])
+        v = torch.linalg.solve_triangular(L, y.expand(batch + y.shape[-1:]).unsqueeze(-1), upper=False)
+        U = torch.linalg.solve_triangular(L, PH.expand(batch + PH.shape[-2:]).transpose(-1, -2),
+                                          upper=False).transpose(-1, -2)
+        lp = lp - 0.5 * v.squeeze(-1).pow(2).sum(-1) - L.diagonal(dim1=-2, dim2=-1).log().sum(-1) \
+            - 0.5 * o * math.log(2 * math.pi)
+        m = mp + (U @ v).squeeze(-1)
+        P = Pp - U @ U.transpose(-1, -2)
+    nan = lp.new_full((), float("nan"))
+    return torch.where(bad, nan, lp), m, P
+
+
+class GaussianHMM(TorchDistribution):
+    """Hidden Markov model with Gaussian initial, transition and observation distributions (reference:
+    pyro/distributions/hmm.py:434-741), the generative model
+
+        z = initial_dist.sample()
+        for t in range(num_steps):
+            z = z @ transition_matrix + transition_dist.sample()
+            x[t] = z @ observation_matrix + observation_dist.sample()
+
+    with ``event_shape = (num_steps, obs_dim)``; time-homogeneous parameters give ``num_steps = 1`` and take data of
+    any length.  Each of the three distributions is a ``MultivariateNormal`` or an ``Independent(Normal, 1)``
+    (this package's classes or torch's).
+
+    ``log_prob`` is differentiable in every parameter and in the value.  Device tensors in float32 / float64 with
+    hidden and obs dimension up to 16 take ONE launch of the Kalman filter / smoother kernel; everything else (CPU
+    tensors, larger dimensions, other dtypes, ``hmm.FUSED_GAUSSIAN_HMM = False``) the sequential torch filter of
+    this module.
+
+    Not built here: ``conjugate_update``, ``rsample_posterior``, ``GammaGaussianHMM``, ``LinearHMM``,
+    ``IndependentHMM``, ``GaussianMRF`` and the HMM reparametrisers."""
+    arg_constraints = {}
+    has_rsample = True
+    support = constraints.independent(constraints.real, 2)
+
+    def __init__(self, initial_dist, transition_matrix, transition_dist, observation_matrix, observation_dist,
+                 validate_args=None, duration=None):
+        if not isinstance(transition_matrix, torch.Tensor) or transition_matrix.dim() < 2:
+            raise ValueError("transition_matrix must be a tensor [..., hidden_dim, hidden_dim]")
+        if not isinstance(observation_matrix, torch.Tensor) or observation_matrix.dim() < 2:
+            raise ValueError("observation_matrix must be a tensor [..., hidden_dim, obs_dim]")
+        m0, P0 = _loc_cov(initial_dist, "initial_dist")
+        q, Q = _loc_cov(transition_dist, "transition_dist")
+        r, R = _loc_cov(observation_dist, "observation_dist")
+        hidden_dim, obs_dim = observation_matrix.shape[-2:]
+        if initial_dist.event_shape != (hidden_dim,) or transition_dist.event_shape != (hidden_dim,) \
+                or transition_matrix.shape[-2:] != (hidden_dim, hidden_dim) \
+                or observation_dist.event_shape != (obs_dim,):
+            raise ValueError("expected initial_dist and transition_dist over {0} dims, transition_matrix "
+                             "[..., {0}, {0}] and observation_dist over {1} dims".format(hidden_dim, obs_dim))
+        # a time axis on everything but the initial state (batch shape () = shared and time-homogeneous)
+        m0 = m0.expand(initial_dist.batch_shape + (hidden_dim,))
+        P0 = P0.expand(initial_dist.batch_shape + (hidden_dim, hidden_dim))
+        F = transition_matrix if transition_matrix.dim() > 2 else transition_matrix.unsqueeze(0)
+        H = observation_matrix if observation_matrix.dim() > 2 else observation_matrix.unsqueeze(0)
+        tb = transition_dist.batch_shape or (1,)
+        ob = observation_dist.batch_shape or (1,)
+        q, Q = q.expand(tb + (hidden_dim,)), Q.expand(tb + (hidden_dim, hidden_dim))
+        r, R = r.expand(ob + (obs_dim,)), R.expand(ob + (obs_dim, obs_dim))
+        self._setup(m0, P0, F, q, Q, H, r, R, duration, validate_args)
+
+    def _setup(self, m0, P0, F, q, Q, H, r, R, duration, validate_args):
+        hidden_dim, obs_dim = H.shape[-2:]
+        shape = torch.broadcast_shapes(m0.shape[:-1] + (1,), F.shape[:-2], q.shape[:-1], H.shape[:-2], r.shape[:-1])
+        batch_shape, time_shape = shape[:-1], shape[-1:]
+        if duration is not None and time_shape[0] not in (1, duration):
+            raise ValueError("duration {} does not match the time axis of size {}".format(duration, time_shape[0]))
+        if duration is None and time_shape[0] != 1:
+            duration = time_shape[0]
+        self.hidden_dim, self.obs_dim, self.duration = hidden_dim, obs_dim, duration
+        self._parts = (m0, P0, F, q, Q, H, r, R)
+        super().__init__(torch.Size(batch_shape), torch.Size(time_shape + (obs_dim,)), validate_args=validate_args)
+
+    @classmethod
+    def _from_parts(cls, parts, duration, validate_args):
+        new = cls.__new__(cls)
+        new._setup(*parts, duration, validate_args)
+        return new
+
+    def expand(self, batch_shape, _instance=None):
+        new = self._get_checked_instance(GaussianHMM, _instance)
+        batch_shape = torch.Size(torch.broadcast_shapes(self.batch_shape, tuple(batch_shape)))
+        m0, P0 = self._parts[:2]
+        # the batch shape is the broadcast of all the parts: expanding the initial state is enough
+        new._parts = (m0.expand(batch_shape + m0.shape[-1:]), P0.expand(batch_shape + P0.shape[-2:])) + self._parts[2:]
+        new.hidden_dim, new.obs_dim, new.duration = self.hidden_dim, self.obs_dim, self.duration
+        super(GaussianHMM, new).__init__(batch_shape, self.event_shape, validate_args=False)
+        new._validate_args = self.__dict__.get("_validate_args")
+        return new
+
+    def _validate_sample(self, value):
+        pass        # time may be longer than event_shape[0] for time-homogeneous parameters
+
+    def _check_value(self, value):
+        if value.dim() < 2 or value.shape[-1] != self.obs_dim:
+            raise ValueError("expected a value [..., num_steps, {}], got {}".format(self.obs_dim, tuple(value.shape)))
+        T = value.shape[-2]
+        for p, nd in zip(self._parts[2:], (2, 1, 2, 2, 1, 2)):
+            if p.shape[-nd - 1] not in (1, T):
+                raise ValueError("a parameter has {} time steps, the data {}".format(p.shape[-nd - 1], T))
+        return torch.broadcast_shapes(self.batch_shape, value.shape[:-2]), T
+
+    def _takes_kernel(self, value):
+        from .. import kernels
+        return (FUSED_GAUSSIAN_HMM and value.dtype in (torch.float32, torch.float64)
+                and all(kernels.on_device(t) and t.dtype == value.dtype for t in self._parts + (value,))
+                and self.hidden_dim <= kernels.GAUSSIAN_HMM_MAX_HIDDEN
+                and self.obs_dim <= kernels.GAUSSIAN_HMM_MAX_OBS)
+
+    def _kernel_inputs(self, value, batch, T):
+        """The parts in the layouts of kernels.gaussian_hmm_fwd_bwd: a parameter whose batch dims are all 1 stays
+        shared ([1, ...], batch stride 0), any other is expanded to the B sequences; the time axis keeps its size."""
+        B = 1
+        for n in batch:
+            B *= int(n)
+        out = []
+        for i, (p, nd) in enumerate(zip(self._parts, (1, 2, 2, 1, 2, 2, 1, 2))):
+            tail = p.shape[-nd - (1 if i >= 2 else 0):]
+            lead = p.shape[:p.dim() - len(tail)]
+            if all(n == 1 for n in lead):
+                out.append(p.reshape((1,) + tuple(tail)).contiguous())
+            else:
+                out.append(p.expand(batch + tuple(tail)).reshape((B,) + tuple(tail)).contiguous())
+        out.append(value.expand(batch + (T, self.obs_dim)).reshape(B, T, self.obs_dim).contiguous())
+        return out
+
+    def log_prob(self, value):
+        batch, T = self._check_value(value)
+        if self._takes_kernel(value):
+            from ..ops.contract import _GaussianHMM
+            return _GaussianHMM.invoke(*self._kernel_inputs(value, batch, T)).reshape(batch)
+        lp, _, _ = _kalman_filter(*self._parts, value)
+        return lp.expand(batch)
+
+    def filter(self, value):
+        """The posterior over the final state given the observations ``value``: a ``MultivariateNormal`` of batch
+        shape ``batch_shape`` that can serve as the ``initial_dist`` of a model of what follows.  It comes from the
+        forward pass alone and is DETACHED from the parameters (the reference's is differentiable)."""
+        from . import MultivariateNormal
+        batch, T = self._check_value(value)
+        with torch.no_grad():
+            if self._takes_kernel(value):
+                from .. import kernels
+                args = [t.detach() for t in self._kernel_inputs(value, batch, T)]
+                _, (m, P), _ = kernels.gaussian_hmm_fwd_bwd(*args, need_grads=False, need_filter=True)
+                m, P = m.reshape(batch + m.shape[-1:]), P.reshape(batch + P.shape[-2:])
+            else:
+                _, m, P = _kalman_filter(*self._parts, value)
+                m, P = m.expand(batch + m.shape[-1:]), P.expand(batch + P.shape[-2:])
+                P = 0.5 * (P + P.transpose(-1, -2))
+        return MultivariateNormal(m, covariance_matrix=P, validate_args=self._validate_args)
+
+    def prefix_condition(self, data):
+        """Given ``event_shape == (t + f, d)`` and ``data`` [..., t, d], the conditional distribution of the
+        remaining ``f`` steps (reference: hmm.py:690-741): ``filter(data)`` under the first ``t`` steps' parameters
+        becomes the initial distribution of the other ``f``."""
+        if self.duration is None:
+            raise ValueError("prefix_condition needs a duration")
+        if data.dim() < 2 or data.size(-1) != self.obs_dim or not data.size(-2) < self.duration:
+            raise ValueError("expected data [..., t < {}, {}], got {}".format(self.duration, self.obs_dim,
+                                                                              tuple(data.shape)))
+        t = data.size(-2)
+        f = self.duration - t
+        left, right = [], []
+        for p, nd in zip(self._parts[2:], (2, 1, 2, 2, 1, 2)):
+            hom = p.shape[-nd - 1] == 1
+            left.append(p if hom else p.narrow(-nd - 1, 0, t))
+            right.append(p if hom else p.narrow(-nd - 1, t, f))
+        post = GaussianHMM._from_parts(self._parts[:2] + tuple(left), t, self._validate_args).filter(data)
+        return GaussianHMM._from_parts((post.loc, post.covariance_matrix) + tuple(right), f, self._validate_args)
+
+    def rsample(self, sample_shape=torch.Size()):
+        """The generative loop with tensor ops on the parameters' device; needs ``duration``."""
+        if self.duration is None:
+            raise ValueError("GaussianHMM.rsample needs a duration (time-homogeneous parameters do not tell it)")
+        m0, P0, F, q, Q, H, r, R = self._parts
+        shape = torch.Size(sample_shape) + self.batch_shape
+
+        def draw(loc, cov):
+            L = torch.linalg.cholesky(cov)
+            eps = torch.randn(shape + loc.shape[-1:], dtype=loc.dtype, device=loc.device)
+            return loc + (L @ eps.unsqueeze(-1)).squeeze(-1)
+
+        z = draw(m0, P0)
+        xs = []
+        for t in range(self.duration):
+            z = (z.unsqueeze(-2) @ _step(F, t, 2)).squeeze(-2) + draw(_step(q, t, 1), _step(Q, t, 2))
+            xs.append((z.unsqueeze(-2) @ _step(H, t, 2)).squeeze(-2) + draw(_step(r, t, 1), _step(R, t, 2)))
+        return torch.stack(xs, dim=-2)

@@ -811,6 +811,76 @@ def logchain_decode(unary, pairwise, mode=0, seed=0, offset=0, offset_dev=None, 
     return z, log_norm
 
 
+# the dimension limits of pa_gaussian_hmm_fwd_bwd (csrc/gaussian_hmm.h: GH_MAXHIDDEN, GH_MAXOBS)
+GAUSSIAN_HMM_MAX_HIDDEN = 16
+GAUSSIAN_HMM_MAX_OBS = 16
+
+
+def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filter=False):
+    """A linear-Gaussian state-space model filtered (and smoothed, for its gradient) in ONE launch
+    (pa_gaussian_hmm_fwd_bwd).  Row vectors: z_0 ~ N(m0, P0), z_t = z_{t-1} F_t + N(q_t, Q_t),
+    x_t = z_t H_t + N(r_t, R_t), t = 1..T.  Contiguous tensors of one dtype:
+
+        m0 [B | 1, h]          P0 [B | 1, h, h]
+        F  [B | 1, T | 1, h, h]    q [B | 1, T | 1, h]    Q [B | 1, T | 1, h, h]
+        H  [B | 1, T | 1, h, o]    r [B | 1, T | 1, o]    R [B | 1, T | 1, o, o]
+        x  [B, T, o]
+
+    A leading 1 is a parameter shared by the sequences (batch stride 0), a 1 on the step axis a time-homogeneous
+    one (step stride 0; with T = 1 every parameter is).  -> (log_prob [B], filt, grads): ``filt`` = (mean [B, h],
+    cov [B, h, h]) of the final state with ``need_filter``, else None; ``grads`` with ``need_grads`` the nine
+    gradients of log_prob[b] in the order of the arguments, [B, ...] for m0 / P0 / x and [B, T | 1, ...] for the
+    others -- the step axis of a time-homogeneous parameter is already summed, the batch axis of a shared one is
+    NOT (the caller sums, as for logchain_fwd_bwd) -- else None.  A sequence with a non-positive pivot gets NaN.
+    hidden or obs over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    _require_gpu(x, *params)
+    assert x.dim() == 3 and x.is_contiguous()
+    B, T, o = x.shape
+    h = m0.shape[-1]
+    assert T >= 1 and h >= 1 and o >= 1
+    if h > GAUSSIAN_HMM_MAX_HIDDEN or o > GAUSSIAN_HMM_MAX_OBS:
+        raise Unsupported("pyro_amd: gaussian_hmm: hidden=%d obs=%d over the limit of %d / %d"
+                          % (h, o, GAUSSIAN_HMM_MAX_HIDDEN, GAUSSIAN_HMM_MAX_OBS))
+    events = ((h,), (h, h), (h, h), (h,), (h, h), (h, o), (o,), (o, o))
+    strides, steps = [], []
+    for i, (p, ev) in enumerate(zip(params, events)):
+        timed = i >= 2
+        assert p.dtype == x.dtype and p.is_contiguous(), "gaussian_hmm: contiguous parameters of x's dtype"
+        assert p.dim() == len(ev) + (2 if timed else 1) and tuple(p.shape[-len(ev):]) == ev, \
+            "gaussian_hmm: parameter %d has shape %s" % (i, tuple(p.shape))
+        assert p.shape[0] in (1, B) and (not timed or p.shape[1] in (1, T))
+        n = 1
+        for d in ev:
+            n *= d
+        Tp = p.shape[1] if timed else 1
+        strides.append(0 if p.shape[0] == 1 else Tp * n)
+        if timed:
+            strides.append(0 if Tp == 1 else n)
+            steps.append(Tp)
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, dtype=x.dtype, device=x.device)     # noqa: E731
+    log_prob = new(B)
+    filt = (new(B, h), new(B, h, h)) if need_filter else None
+    grads = None
+    if need_grads:
+        grads = (new(B, h), new(B, h, h), new(B, steps[0], h, h), new(B, steps[1], h), new(B, steps[2], h, h),
+                 new(B, steps[3], h, o), new(B, steps[4], o), new(B, steps[5], o, o), new(B, T, o))
+    nbytes = lib.pa_gaussian_hmm_workspace(_dtype(x), B, T, h, o, int(need_grads))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    args = [_dtype(x), _ptr(m0), strides[0], _ptr(P0), strides[1]]
+    k = 2
+    for p in params[2:]:
+        args += [_ptr(p), strides[k], strides[k + 1]]
+        k += 2
+    args += [_ptr(x), B, T, h, o, _ptr(log_prob)]
+    args += [_ptr(t) for t in (filt or (None, None))]
+    args += [_ptr(g) for g in (grads or (None,) * 9)]
+    args += [_ptr(ws), nbytes, _stream()]
+    check(lib.pa_gaussian_hmm_fwd_bwd(*args))
+    return log_prob, filt, grads
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.

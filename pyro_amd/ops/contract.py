@@ -502,6 +502,35 @@ class _LogChain(torch.autograd.Function):
         return g.reshape(-1, 1, 1) * g_u, d_pair
 
 
+@_dispatcher_op("gaussian_hmm")
+class _GaussianHMM(torch.autograd.Function):
+    """log p(x) of a linear-Gaussian state-space model for every sequence (Kalman filter) with the smoother's
+    expected complete-data score as gradient, ONE launch (pa_gaussian_hmm_fwd_bwd).  Arguments in the layouts of
+    kernels.gaussian_hmm_fwd_bwd."""
+
+    @staticmethod
+    def forward(ctx, m0, P0, F, q, Q, H, r, R, x):
+        need = any(ctx.needs_input_grad)
+        log_prob, _, grads = kernels.gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=need)
+        if need:
+            ctx.save_for_backward(*grads)
+        ctx.shapes = tuple(t.shape for t in (m0, P0, F, q, Q, H, r, R, x))
+        return log_prob
+
+    @staticmethod
+    def backward(ctx, g):
+        from ..distributions.fused import _sum_to
+        out = []
+        for grad, shape, needed in zip(ctx.saved_tensors, ctx.shapes, ctx.needs_input_grad):
+            if not needed:
+                out.append(None)
+                continue
+            d = g.reshape((-1,) + (1,) * (grad.dim() - 1)) * grad
+            # a parameter shared by the sequences: the sum over them is ours (the steps were summed in the kernel)
+            out.append(_sum_to(d, d.new_empty(shape)) if d.shape != shape else d)
+        return tuple(out)
+
+
 def _match_chain(terms, sum_ids, ready=None):
     """The pattern of the chain kernels: a component whose names form a simple path (every term mentions one or two
     of them, the two-name terms link consecutive variables: an HMM written with pyro.markov), at most 64 states, one

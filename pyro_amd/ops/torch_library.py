@@ -124,6 +124,18 @@ def _register():
         B, T, _K = unary.shape
         return unary.new_empty((B, T), dtype=torch.int64), unary.new_empty((B,))
 
+    @lib.register_fake("pyro_amd::gaussian_hmm")
+    def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, x, need_grads):
+        B, T, o = x.shape
+        h = m0.shape[-1]
+        grads = []
+        if need_grads:
+            steps = [t.shape[1] for t in (trans, trans_loc, trans_cov, obs, obs_loc, obs_cov)]
+            grads = [x.new_empty((B, h)), x.new_empty((B, h, h)), x.new_empty((B, steps[0], h, h)),
+                     x.new_empty((B, steps[1], h)), x.new_empty((B, steps[2], h, h)), x.new_empty((B, steps[3], h, o)),
+                     x.new_empty((B, steps[4], o)), x.new_empty((B, steps[5], o, o)), x.new_empty((B, T, o))]
+        return x.new_empty((B,)), x.new_empty((B, h)), x.new_empty((B, h, h)), grads
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -605,4 +617,4 @@ def registered_ops():
 # the typed C++ ops of csrc/torch_ops.cpp beside the GLM site's (round 6): real argument lists, loadable from C++
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
-             "nuts_tree_run_advance")
+             "nuts_tree_run_advance", "gaussian_hmm")
