@@ -929,6 +929,34 @@ int pa_gaussian_hmm_fwd_bwd(int dtype, const void* m0, int64_t m0_stride_batch, 
                             void* grad_H, void* grad_r, void* grad_R, void* grad_x, void* workspace,
                             size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gaussian_hmm_sample.hip: draws of the latent path of that model given the data -------------------------
+ * Replaces GaussianHMM.rsample_posterior (pyro/distributions/hmm.py:596-604 over sequential_gaussian_filter_sample,
+ * pyro/ops/gaussian.py:600: a parallel-scan forward filter with a tape, then as many rounds of conditional draws)
+ * with two launches on the caller's stream.  Parameters, strides and x as for pa_gaussian_hmm_fwd_bwd.
+ * Launch 1, one wave per sequence: the same Kalman filter, then backward, with the states as columns, the maps of
+ *   z_T = c_T + L_T eps_T,   z_{t-1} = c_{t-1} + G_{t-1} z_t + L_{t-1} eps_{t-1},   t = T..2          (G_T = 0)
+ *   G = P_{t-1} F (P^p)^-1,  c_{t-1} = m_{t-1} - G m^p,  L_{t-1} L_{t-1}^T = sym((I - G F^T) P_{t-1} (I - G F^T)^T + G Q G^T)
+ * (the conditional covariance in Joseph form; L_T L_T^T = sym(P_T)).  z_0 is not drawn.
+ *   maps_c [B, T, hidden], maps_G, maps_L [B, T, hidden, hidden] (all three or none; L lower triangular, zeros above):
+ *     where to keep the maps; without them they live in the workspace.
+ * Launch 2, one lane per draw: z[s, b, t, :] from the standard normal eps[s, b, t, :]; eps and z are [S, B, T, hidden]
+ *   contiguous (S = 0: not read; eps of zeros gives the posterior mean).
+ * A sequence with a non-positive pivot in the filter or in a Cholesky factor of P^p, P_T or a conditional covariance
+ * gets NaN maps and paths; other sequences are untouched.  No atomics: bit-reproducible, and a draw does not depend
+ * on S.  hidden or obs > 16: PA_ERR_UNSUPPORTED.  B = 0, or S = 0 without maps: PA_OK without a launch; S = 0 with
+ * maps: launch 1 alone.
+ * workspace: pa_gaussian_hmm_sample_workspace(...) bytes -- B T (hidden + hidden^2) elements of filtered moments and
+ * B T (hidden + 2 hidden^2) of maps (unused when the caller keeps the maps). */
+size_t pa_gaussian_hmm_sample_workspace(int dtype, int64_t B, int64_t T, int64_t hidden, int64_t obs);
+int pa_gaussian_hmm_sample(int dtype, const void* m0, int64_t m0_stride_batch, const void* P0,
+                           int64_t P0_stride_batch, const void* F, int64_t F_stride_batch, int64_t F_stride_step,
+                           const void* q, int64_t q_stride_batch, int64_t q_stride_step, const void* Q,
+                           int64_t Q_stride_batch, int64_t Q_stride_step, const void* H, int64_t H_stride_batch,
+                           int64_t H_stride_step, const void* r, int64_t r_stride_batch, int64_t r_stride_step,
+                           const void* R, int64_t R_stride_batch, int64_t R_stride_step, const void* x, int64_t B,
+                           int64_t T, int64_t hidden, int64_t obs, int64_t S, const void* eps, void* z, void* maps_c,
+                           void* maps_G, void* maps_L, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

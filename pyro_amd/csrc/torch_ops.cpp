@@ -386,16 +386,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> logchain(const at::Tensor& unary,
 // kernels.gaussian_hmm_fwd_bwd: m0 [B | 1, h], P0 [B | 1, h, h], the six others [B | 1, T | 1, ...], x [B, T, o];
 // grads: empty without need_grads, else in the order of the arguments (a step axis of 1 is already summed, a batch
 // axis that the parameter shares is not)
-std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian_hmm(
-    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
-    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov,
-    const at::Tensor& x, bool need_grads) {
-  const int dt = dtype_of(x, "gaussian_hmm");
+struct GhmmLayout {
+  int dt;
+  int64_t B, T, h, o, sb[8], ss[8], steps[8];
+};
+GhmmLayout gaussian_hmm_layout(const at::Tensor* const* p, const at::Tensor& x) {
+  GhmmLayout l;
+  l.dt = dtype_of(x, "gaussian_hmm");
+  const at::Tensor& m0 = *p[0];
   TORCH_CHECK(x.dim() == 3 && x.is_contiguous() && m0.dim() == 2, "pyro_amd::gaussian_hmm: x [B, T, obs] contiguous, m0 [B | 1, hidden]");
-  const int64_t B = x.size(0), T = x.size(1), o = x.size(2), h = m0.size(1);
-  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const int64_t B = l.B = x.size(0), T = l.T = x.size(1), o = l.o = x.size(2), h = l.h = m0.size(1);
   const std::vector<int64_t> ev[8] = {{h}, {h, h}, {h, h}, {h}, {h, h}, {h, o}, {o}, {o, o}};
-  int64_t sb[8], ss[8], steps[8];
+  int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss, (&steps)[8] = l.steps;
   for (int i = 0; i < 8; ++i) {
     const at::Tensor& t = *p[i];
     const int64_t lead = i < 2 ? 1 : 2, nd = lead + (int64_t)ev[i].size();
@@ -412,6 +414,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian
     sb[i] = t.size(0) == 1 ? 0 : steps[i] * n;
     ss[i] = steps[i] == 1 ? 0 : n;
   }
+  return l;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian_hmm(
+    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
+    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov,
+    const at::Tensor& x, bool need_grads) {
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const GhmmLayout l = gaussian_hmm_layout(p, x);
+  const int dt = l.dt;
+  const int64_t B = l.B, T = l.T, h = l.h, o = l.o;
+  const int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss, (&steps)[8] = l.steps;
   const auto opt = x.options();
   at::Tensor log_prob = at::empty({B}, opt), fm = at::empty({B, h}, opt), fP = at::empty({B, h, h}, opt);
   std::vector<at::Tensor> g;
@@ -431,6 +445,39 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian
                                 current_stream()),
         "gaussian_hmm");
   return {log_prob, fm, fP, g};
+}
+
+// draws of that model's latent path given the data, forward filter and backward sample in two launches
+// (pyro/distributions/hmm.py:596-604 GaussianHMM.rsample_posterior over pyro/ops/gaussian.py:600
+// sequential_gaussian_filter_sample).  Layouts as kernels.gaussian_hmm_sample: the parameters and x as above, eps
+// [S, B, T, h] standard normal -> z [S, B, T, h] and, with need_maps, the maps (c [B, T, h], G, L [B, T, h, h]) of
+// z_T = c_T + L_T eps_T, z_{t-1} = c_{t-1} + G_{t-1} z_t + L_{t-1} eps_{t-1} (empty without)
+std::tuple<at::Tensor, std::vector<at::Tensor>> gaussian_hmm_sample(
+    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
+    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov,
+    const at::Tensor& x, const at::Tensor& eps, bool need_maps) {
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const GhmmLayout l = gaussian_hmm_layout(p, x);
+  const int64_t B = l.B, T = l.T, h = l.h, o = l.o;
+  const int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss;
+  TORCH_CHECK(eps.is_cuda() && eps.scalar_type() == x.scalar_type() && eps.is_contiguous() && eps.dim() == 4 &&
+                  eps.size(1) == B && eps.size(2) == T && eps.size(3) == h,
+              "pyro_amd::gaussian_hmm_sample: eps [S, B, T, hidden] contiguous of x's dtype");
+  const int64_t S = eps.size(0);
+  const auto opt = x.options();
+  at::Tensor z = at::empty({S, B, T, h}, opt);
+  std::vector<at::Tensor> maps;
+  if (need_maps) maps = {at::empty({B, T, h}, opt), at::empty({B, T, h, h}, opt), at::empty({B, T, h, h}, opt)};
+  auto mp = [&](int i) { return need_maps ? maps[i].data_ptr() : nullptr; };
+  const size_t ws_bytes = pa_gaussian_hmm_sample_workspace(l.dt, B, T, h, o);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, opt.dtype(at::kByte));
+  check(pa_gaussian_hmm_sample(l.dt, m0.data_ptr(), sb[0], P0.data_ptr(), sb[1], trans.data_ptr(), sb[2], ss[2],
+                               trans_loc.data_ptr(), sb[3], ss[3], trans_cov.data_ptr(), sb[4], ss[4], obs.data_ptr(),
+                               sb[5], ss[5], obs_loc.data_ptr(), sb[6], ss[6], obs_cov.data_ptr(), sb[7], ss[7],
+                               x.data_ptr(), B, T, h, o, S, eps.data_ptr(), z.data_ptr(), mp(0), mp(1), mp(2),
+                               ws.data_ptr(), ws_bytes, current_stream()),
+        "gaussian_hmm_sample");
+  return {z, maps};
 }
 
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
@@ -610,6 +657,8 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("gaussian_hmm(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, Tensor x, bool need_grads) -> (Tensor log_prob, Tensor filter_mean, "
         "Tensor filter_cov, Tensor[] grads)");
+  m.def("gaussian_hmm_sample(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
+        "Tensor obs_loc, Tensor obs_cov, Tensor x, Tensor eps, bool need_maps) -> (Tensor z, Tensor[] maps)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -639,6 +688,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("logchain", &logchain);
   m.impl("logchain_decode", &logchain_decode);
   m.impl("gaussian_hmm", &gaussian_hmm);
+  m.impl("gaussian_hmm_sample", &gaussian_hmm_sample);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

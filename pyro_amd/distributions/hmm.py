@@ -13,7 +13,8 @@ returns the log-likelihood of every batch element and, as its gradient, the post
 GaussianHMM: linear-Gaussian state-space model (reference: pyro/distributions/hmm.py:434-741).  The reference
 eliminates time with sequential_gaussian_tensordot (O(log T) rounds of batched Gaussian contractions); here
 log_prob is ONE launch of the Kalman filter / Rauch-Tung-Striebel kernel (pa_gaussian_hmm_fwd_bwd), whose
-smoother pass hands back the gradient with respect to every parameter and the data.  Whatever the kernel does
+smoother pass hands back the gradient with respect to every parameter and the data; rsample_posterior is the same
+filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample).  Whatever the kernels do
 not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
 the plain-torch sequential filter of this file, differentiated by autograd.
 """
@@ -178,11 +179,11 @@ def _step(p, t, nd):
     return p.select(-nd - 1, t if p.shape[-nd - 1] > 1 else 0)
 
 
-def _kalman_filter(m0, P0, F, q, Q, H, r, R, x):
+def _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=None):
     """The sequential filter in plain torch ops: parameters broadcastable to [..., T | 1, ...] (m0, P0 without the
     time axis), x [..., T, obs] -> (log_prob [...], filtered mean and covariance of the last state).  The same
     arithmetic as csrc/gaussian_hmm.hip: P^p symmetrised, S = L L^T, U = P^p H L^-T, P = P^p - U U^T.  A step
-    whose S is not positive definite makes the element NaN."""
+    whose S is not positive definite makes the element NaN.  ``keep``: a list that receives every step's (m_t, P_t)."""
     T, o = x.shape[-2:]
     m, P = m0, P0
     lp, bad = 0.0, False
@@ -206,8 +207,68 @@ def _kalman_filter(m0, P0, F, q, Q, H, r, R, x):
             - 0.5 * o * math.log(2 * math.pi)
         m = mp + (U @ v).squeeze(-1)
         P = Pp - U @ U.transpose(-1, -2)
+        if keep is not None:
+            keep.append((m, P))
     nan = lp.new_full((), float("nan"))
     return torch.where(bad, nan, lp), m, P
+
+
+def _backward_sample_maps(m0, P0, F, q, Q, H, r, R, x):
+    """The posterior of the path z_1..z_T given x as a chain run backward, in plain torch ops and with the states
+    written as columns: z_T = c_T + L_T eps_T, z_{t-1} = c_{t-1} + G_{t-1} z_t + L_{t-1} eps_{t-1}.  Arguments as
+    for _kalman_filter -> (c [..., T, h], G [..., T, h, h] with G_T = 0, L [..., T, h, h] lower triangular).  The
+    same arithmetic as csrc/gaussian_hmm_sample.hip: the filter above keeps (m_t, P_t); L_T = chol(sym(P_T)); for
+    t = T..2, with m^p, P^p predicted from (m_{t-1}, P_{t-1}) as the filter does,
+        G = P_{t-1} F (P^p)^-1,   c_{t-1} = m_{t-1} - G m^p,   J = I - G F^T,
+        L_{t-1} = chol(sym(J P_{t-1} J^T + G Q G^T))
+    -- the conditional covariance in Joseph form, a sum of two positive semi-definite terms: P_{t-1} - G P^p G^T
+    loses positive definiteness in float32 when Q is nearly singular.  An element with a non-positive pivot, in the
+    filter or in a factor here, is NaN throughout."""
+    T = x.shape[-2]
+    kept = []
+    lp, _, _ = _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=kept)
+    bad = torch.isnan(lp)
+    batch = lp.shape
+    m, P = kept[-1]
+    h = m.shape[-1]
+    L, info = torch.linalg.cholesky_ex(0.5 * (P + P.transpose(-1, -2)))
+    bad = (info > 0) | bad
+    eye = torch.eye(h, dtype=m.dtype, device=m.device)
+    cs, Gs, Ls = [m.expand(batch + (h,))], [torch.zeros_like(P).expand(batch + (h, h))], [L.expand(batch + (h, h))]
+    for t in range(T - 1, 0, -1):
+        m, P = kept[t - 1]
+        Ft, qt, Qt = _step(F, t, 2), _step(q, t, 1), _step(Q, t, 2)
+        mp = (m.unsqueeze(-2) @ Ft).squeeze(-2) + qt
+        FtP = Ft.transpose(-1, -2) @ P
+        Pp = FtP @ Ft + Qt
+        Pp = 0.5 * (Pp + Pp.transpose(-1, -2))
+        Lp, info = torch.linalg.cholesky_ex(Pp)
+        bad = (info > 0) | bad
+        G = torch.cholesky_solve(FtP, Lp).transpose(-1, -2)
+        J = eye - G @ Ft.transpose(-1, -2)
+        C = (J @ P) @ J.transpose(-1, -2) + (G @ Qt) @ G.transpose(-1, -2)
+        L, info = torch.linalg.cholesky_ex(0.5 * (C + C.transpose(-1, -2)))
+        bad = (info > 0) | bad
+        cs.append((m - (G @ mp.unsqueeze(-1)).squeeze(-1)).expand(batch + (h,)))
+        Gs.append(G.expand(batch + (h, h)))
+        Ls.append(L.expand(batch + (h, h)))
+    c, G, L = (torch.stack(v[::-1], dim=len(batch)) for v in (cs, Gs, Ls))
+    nan = c.new_full((), float("nan"))
+    return (torch.where(bad[..., None, None], nan, c), torch.where(bad[..., None, None, None], nan, G),
+            torch.where(bad[..., None, None, None], nan, L))
+
+
+def _backward_sample(c, G, L, eps):
+    """The paths [..., T, h] of the maps for the standard normal ``eps`` [sample_shape, ..., T, h]."""
+    T = eps.shape[-2]
+    z, out = None, []
+    for t in range(T - 1, -1, -1):
+        zt = c[..., t, :] + (L[..., t, :, :] @ eps[..., t, :, None]).squeeze(-1)
+        if z is not None:
+            zt = zt + (G[..., t, :, :] @ z.unsqueeze(-1)).squeeze(-1)
+        z = zt
+        out.append(z)
+    return torch.stack(out[::-1], dim=-2)
 
 
 class GaussianHMM(TorchDistribution):
@@ -228,8 +289,11 @@ class GaussianHMM(TorchDistribution):
     tensors, larger dimensions, other dtypes, ``hmm.FUSED_GAUSSIAN_HMM = False``) the sequential torch filter of
     this module.
 
-    Not built here: ``conjugate_update``, ``rsample_posterior``, ``GammaGaussianHMM``, ``LinearHMM``,
-    ``IndependentHMM``, ``GaussianMRF`` and the HMM reparametrisers."""
+    ``rsample_posterior`` draws the whole latent path given the data: two launches (csrc/gaussian_hmm_sample.hip) for
+    the same tensors when nothing needs a gradient, the backward-sampling loop of this module otherwise.
+
+    Not built here: ``conjugate_update``, ``GammaGaussianHMM``, ``LinearHMM``, ``IndependentHMM``, ``GaussianMRF``
+    and the HMM reparametrisers."""
     arg_constraints = {}
     has_rsample = True
     support = constraints.independent(constraints.real, 2)
@@ -350,6 +414,40 @@ class GaussianHMM(TorchDistribution):
                 m, P = m.expand(batch + m.shape[-1:]), P.expand(batch + P.shape[-2:])
                 P = 0.5 * (P + P.transpose(-1, -2))
         return MultivariateNormal(m, covariance_matrix=P, validate_args=self._validate_args)
+
+    def rsample_posterior(self, value, sample_shape=torch.Size(), *, noise=None):
+        """Draws of the latent path ``z_1..z_T`` given the observations ``value`` [..., T, obs_dim] (reference:
+        hmm.py:596-604): a tensor of shape ``sample_shape + batch + (T, hidden_dim)`` with ``batch`` the broadcast of
+        ``batch_shape`` and ``value.shape[:-2]``.  The initial state ``z_0`` is not drawn, as in the reference.
+
+        ``noise``: standard normal of the output's shape; drawn with ``torch.randn`` on the parameters' device when
+        not given, so ``torch.manual_seed`` reproduces a call; zeros give the posterior mean.  (The reference's
+        method has no such argument, its ops function does.)  The map from noise to path is this package's:
+        sequential, ``z_T`` first and every earlier state given the next one, over T rows of noise -- not the
+        reference's parallel scan over T + 1 rows.  The distribution of the paths is the same.
+
+        With grad mode on and a parameter, ``value`` or ``noise`` requiring a gradient the draws are reparameterised:
+        the torch route, differentiable in all of them (it also serves CPU tensors, dimensions over 16, other dtypes
+        and ``hmm.FUSED_GAUSSIAN_HMM = False``).  Otherwise device tensors within the kernel's limits take the two
+        launches of csrc/gaussian_hmm_sample.hip and the result is DETACHED, like ``filter``'s.  A series with a
+        non-positive pivot has NaN paths."""
+        batch, T = self._check_value(value)
+        shape = torch.Size(sample_shape) + batch + (T, self.hidden_dim)
+        if noise is None:
+            noise = torch.randn(shape, dtype=value.dtype, device=self._parts[0].device)
+        elif noise.shape != shape:
+            raise ValueError("expected noise of shape {}, got {}".format(tuple(shape), tuple(noise.shape)))
+        tensors = self._parts + (value, noise)
+        needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+        from .. import kernels
+        if (not needs_grad and self._takes_kernel(value) and kernels.on_device(noise)
+                and noise.dtype == value.dtype):
+            args = [t.detach() for t in self._kernel_inputs(value, batch, T)]
+            eps = noise.detach().reshape((-1,) + tuple(args[-1].shape[:2]) + (self.hidden_dim,)).contiguous()
+            z, _ = kernels.gaussian_hmm_sample(*args, eps)
+            return z.reshape(shape)
+        c, G, L = _backward_sample_maps(*self._parts, value)
+        return _backward_sample(c, G, L, noise).expand(shape)
 
     def prefix_condition(self, data):
         """Given ``event_shape == (t + f, d)`` and ``data`` [..., t, d], the conditional distribution of the

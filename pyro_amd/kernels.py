@@ -816,28 +816,13 @@ GAUSSIAN_HMM_MAX_HIDDEN = 16
 GAUSSIAN_HMM_MAX_OBS = 16
 
 
-def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filter=False):
-    """A linear-Gaussian state-space model filtered (and smoothed, for its gradient) in ONE launch
-    (pa_gaussian_hmm_fwd_bwd).  Row vectors: z_0 ~ N(m0, P0), z_t = z_{t-1} F_t + N(q_t, Q_t),
-    x_t = z_t H_t + N(r_t, R_t), t = 1..T.  Contiguous tensors of one dtype:
-
-        m0 [B | 1, h]          P0 [B | 1, h, h]
-        F  [B | 1, T | 1, h, h]    q [B | 1, T | 1, h]    Q [B | 1, T | 1, h, h]
-        H  [B | 1, T | 1, h, o]    r [B | 1, T | 1, o]    R [B | 1, T | 1, o, o]
-        x  [B, T, o]
-
-    A leading 1 is a parameter shared by the sequences (batch stride 0), a 1 on the step axis a time-homogeneous
-    one (step stride 0; with T = 1 every parameter is).  -> (log_prob [B], filt, grads): ``filt`` = (mean [B, h],
-    cov [B, h, h]) of the final state with ``need_filter``, else None; ``grads`` with ``need_grads`` the nine
-    gradients of log_prob[b] in the order of the arguments, [B, ...] for m0 / P0 / x and [B, T | 1, ...] for the
-    others -- the step axis of a time-homogeneous parameter is already summed, the batch axis of a shared one is
-    NOT (the caller sums, as for logchain_fwd_bwd) -- else None.  A sequence with a non-positive pivot gets NaN.
-    hidden or obs over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
-    params = (m0, P0, F, q, Q, H, r, R)
+def _gaussian_hmm_layout(params, x):
+    """The checks the two state-space wrappers share -> (B, T, hidden, obs, the fourteen element strides in the order
+    of the C arguments, the step-axis sizes of the six timed parameters)."""
     _require_gpu(x, *params)
     assert x.dim() == 3 and x.is_contiguous()
     B, T, o = x.shape
-    h = m0.shape[-1]
+    h = params[0].shape[-1]
     assert T >= 1 and h >= 1 and o >= 1
     if h > GAUSSIAN_HMM_MAX_HIDDEN or o > GAUSSIAN_HMM_MAX_OBS:
         raise Unsupported("pyro_amd: gaussian_hmm: hidden=%d obs=%d over the limit of %d / %d"
@@ -858,6 +843,38 @@ def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filt
         if timed:
             strides.append(0 if Tp == 1 else n)
             steps.append(Tp)
+    return B, T, h, o, strides, steps
+
+
+def _gaussian_hmm_args(params, x, strides, B, T, h, o):
+    """The leading C arguments of both entry points: dtype, the parameters with their strides, x and the sizes."""
+    args = [_dtype(x), _ptr(params[0]), strides[0], _ptr(params[1]), strides[1]]
+    k = 2
+    for p in params[2:]:
+        args += [_ptr(p), strides[k], strides[k + 1]]
+        k += 2
+    return args + [_ptr(x), B, T, h, o]
+
+
+def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filter=False):
+    """A linear-Gaussian state-space model filtered (and smoothed, for its gradient) in ONE launch
+    (pa_gaussian_hmm_fwd_bwd).  Row vectors: z_0 ~ N(m0, P0), z_t = z_{t-1} F_t + N(q_t, Q_t),
+    x_t = z_t H_t + N(r_t, R_t), t = 1..T.  Contiguous tensors of one dtype:
+
+        m0 [B | 1, h]          P0 [B | 1, h, h]
+        F  [B | 1, T | 1, h, h]    q [B | 1, T | 1, h]    Q [B | 1, T | 1, h, h]
+        H  [B | 1, T | 1, h, o]    r [B | 1, T | 1, o]    R [B | 1, T | 1, o, o]
+        x  [B, T, o]
+
+    A leading 1 is a parameter shared by the sequences (batch stride 0), a 1 on the step axis a time-homogeneous
+    one (step stride 0; with T = 1 every parameter is).  -> (log_prob [B], filt, grads): ``filt`` = (mean [B, h],
+    cov [B, h, h]) of the final state with ``need_filter``, else None; ``grads`` with ``need_grads`` the nine
+    gradients of log_prob[b] in the order of the arguments, [B, ...] for m0 / P0 / x and [B, T | 1, ...] for the
+    others -- the step axis of a time-homogeneous parameter is already summed, the batch axis of a shared one is
+    NOT (the caller sums, as for logchain_fwd_bwd) -- else None.  A sequence with a non-positive pivot gets NaN.
+    hidden or obs over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    B, T, h, o, strides, steps = _gaussian_hmm_layout(params, x)
     lib = _lib.load()
     new = lambda *shape: torch.empty(shape, dtype=x.dtype, device=x.device)     # noqa: E731
     log_prob = new(B)
@@ -868,17 +885,39 @@ def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filt
                  new(B, steps[3], h, o), new(B, steps[4], o), new(B, steps[5], o, o), new(B, T, o))
     nbytes = lib.pa_gaussian_hmm_workspace(_dtype(x), B, T, h, o, int(need_grads))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
-    args = [_dtype(x), _ptr(m0), strides[0], _ptr(P0), strides[1]]
-    k = 2
-    for p in params[2:]:
-        args += [_ptr(p), strides[k], strides[k + 1]]
-        k += 2
-    args += [_ptr(x), B, T, h, o, _ptr(log_prob)]
+    args = _gaussian_hmm_args(params, x, strides, B, T, h, o) + [_ptr(log_prob)]
     args += [_ptr(t) for t in (filt or (None, None))]
     args += [_ptr(g) for g in (grads or (None,) * 9)]
     args += [_ptr(ws), nbytes, _stream()]
     check(lib.pa_gaussian_hmm_fwd_bwd(*args))
     return log_prob, filt, grads
+
+
+def gaussian_hmm_sample(m0, P0, F, q, Q, H, r, R, x, eps, need_maps=False):
+    """Draws of the latent path z_1..z_T of that model given the data x, forward filter and backward sample in two
+    launches (pa_gaussian_hmm_sample).  Parameters and x in the layouts of gaussian_hmm_fwd_bwd; ``eps`` [S, B, T, h]
+    contiguous, standard normal (zeros give the posterior mean).  -> (z [S, B, T, h], maps): with the states as
+    columns z_T = c_T + L_T eps_T and z_{t-1} = c_{t-1} + G_{t-1} z_t + L_{t-1} eps_{t-1}; ``maps`` = (c [B, T, h],
+    G [B, T, h, h], L [B, T, h, h]) with ``need_maps`` (G_T = 0, L lower triangular), else None.  z_0 is not drawn.
+    A sequence with a non-positive pivot gets NaN maps and paths.  Nothing here is differentiable.  hidden or obs
+    over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    B, T, h, o, strides, _ = _gaussian_hmm_layout(params, x)
+    _require_gpu(eps)
+    assert eps.dim() == 4 and tuple(eps.shape[1:]) == (B, T, h) and eps.dtype == x.dtype and eps.is_contiguous(), \
+        "gaussian_hmm_sample: eps [S, B, T, hidden] contiguous of x's dtype"
+    S = eps.shape[0]
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, dtype=x.dtype, device=x.device)     # noqa: E731
+    z = new(S, B, T, h)
+    maps = (new(B, T, h), new(B, T, h, h), new(B, T, h, h)) if need_maps else None
+    nbytes = lib.pa_gaussian_hmm_sample_workspace(_dtype(x), B, T, h, o)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    args = _gaussian_hmm_args(params, x, strides, B, T, h, o) + [S, _ptr(eps), _ptr(z)]
+    args += [_ptr(t) for t in (maps or (None, None, None))]
+    args += [_ptr(ws), nbytes, _stream()]
+    check(lib.pa_gaussian_hmm_sample(*args))
+    return z, maps
 
 
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):

@@ -136,6 +136,13 @@ def _register():
                      x.new_empty((B, steps[4], o)), x.new_empty((B, steps[5], o, o)), x.new_empty((B, T, o))]
         return x.new_empty((B,)), x.new_empty((B, h)), x.new_empty((B, h, h)), grads
 
+    @lib.register_fake("pyro_amd::gaussian_hmm_sample")
+    def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, x, eps, need_maps):
+        B, T, _o = x.shape
+        h = m0.shape[-1]
+        maps = [x.new_empty((B, T, h)), x.new_empty((B, T, h, h)), x.new_empty((B, T, h, h))] if need_maps else []
+        return x.new_empty((eps.shape[0], B, T, h)), maps
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -617,4 +624,4 @@ def registered_ops():
 # the typed C++ ops of csrc/torch_ops.cpp beside the GLM site's (round 6): real argument lists, loadable from C++
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
-             "nuts_tree_run_advance", "gaussian_hmm")
+             "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample")
