@@ -10,13 +10,11 @@
 // of the log-likelihood (Fisher's identity) -- the relation logchain.hip uses for the discrete chain: the posteriors
 // are the gradient.
 //
-// Forward, per step:  m^p = m F + q,  P^p = sym(F^T P F + Q),  y = x - m^p H - r,  S = H^T P^p H + R = L L^T,
-//     U = P^p H L^-T,  v = L^-1 y,  log_prob += -|v|^2 / 2 - sum log diag L - obs / 2 log 2 pi,
-//     m = m^p + U v,  P = P^p - U U^T.
-// Symmetry: P^p is SYMMETRISED ((A + A^T) / 2 after the two products) and the update subtracts U U^T, which is
-// symmetric by construction; there is no Joseph form.  A non-positive (or NaN) pivot of S marks the sequence: its
-// log_prob, filter outputs and gradients are NaN, no other sequence sees it.  The backward sweep marks a sequence
-// the same way on a bad pivot of P^p, Q, R or P0 (gradients only: log_prob is what the forward pass alone gives).
+// Forward: the filter of gaussian_hmm.h (GhFilter: the recurrence, where P^p is symmetrised, the bad-pivot rule), shared
+// with gaussian_hmm_sample.hip; per step this kernel adds  log_prob += -|v|^2 / 2 - sum log diag L - obs / 2 log 2 pi.
+// A sequence the filter marks (a non-positive or NaN pivot of S) has NaN log_prob, filter outputs and gradients, no
+// other sequence sees it.  The backward sweep marks a sequence the same way on a bad pivot of P^p, Q, R or P0
+// (gradients only: log_prob is what the forward pass alone gives).
 //
 // Backward, per step t = T..1, from the filtered (m_{t-1}, P_{t-1}) kept in the workspace (hidden + hidden^2
 // elements per step; the predicted moments are recomputed): smoother gain G = P_{t-1} F (P^p)^-1,
@@ -31,11 +29,12 @@
 // while the current step computes and are written to LDS at the top of the next step.
 //
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage), one wave of 64 lanes per block:
-//     instantiation    VGPRs  SGPRs  scratch   LDS bytes   waves / SIMD
-//     <float , 8>      162    106    0         5832        3
-//     <float , 16>     256    106    0         21384       1
-//     <double, 8>      172    106    0         11664       2
-//     <double, 16>     256    106    0         42768       1
+//     instantiation    VGPRs      SGPRs  scratch   LDS bytes   waves / SIMD
+//     <float , 8>      132        106    0         5832        3
+//     <float , 16>     256 + 12   106    0         21384       1
+//     <double, 8>      172        106    0         11664       2
+//     <double, 16>     256 + 65   106    0         42768       1
+// (+ n: accumulation registers the 16-wide instantiations use as spill space; nothing goes to scratch memory)
 #include <limits>
 
 #include "common.h"
@@ -44,9 +43,8 @@
 namespace pa {
 
 struct GhmmArgs {
-  const void *m0, *P0, *F, *q, *Q, *H, *r, *R, *x;
-  int64_t m0_sb, P0_sb, F_sb, F_ss, q_sb, q_ss, Q_sb, Q_ss, H_sb, H_ss, r_sb, r_ss, R_sb, R_ss;
-  int T, h, o, grads;
+  GhModel m;
+  int grads;
   void *lp, *fm, *fP, *g_m0, *g_P0, *g_F, *g_q, *g_Q, *g_H, *g_r, *g_R, *g_x, *ws;
 };
 
@@ -55,17 +53,13 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   constexpr int LD = MD + 1, MS = MD * LD, EPL = MD * MD / 64;
   constexpr int NMAT = 19, NVEC = 11;
   __shared__ T sm[NMAT * MS + NVEC * MD + 2];
-  T* const sP = sm;            // filtered covariance P_t (backward: P_{t-1})
-  T* const sF = sP + MS;
-  T* const sQ = sF + MS;
-  T* const sH = sQ + MS;
-  T* const sR = sH + MS;
-  T* const sPp = sR + MS;      // predicted covariance (backward, late: R^-1 V)
-  T* const sL = sPp + MS;      // Cholesky factors
-  T* const sA = sL + MS;       // F^T P; backward: G^T
-  T* const sB = sA + MS;       // P^p H -> U; backward temporaries
-  T* const sC = sB + MS;
-  T* const sX = sC + MS;       // cross-covariance C_t
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  GhFilter<T, MD> f(a.m, sm, sm + NMAT * MS, sm + NMAT * MS + NVEC * MD, lane, b);
+  // the filter's matrices (backward: sP = P_{t-1}, sPp late R^-1 V, sA = G^T, sB and sC temporaries) ...
+  T *const sP = f.sP, *const sF = f.sF, *const sQ = f.sQ, *const sH = f.sH, *const sR = f.sR, *const sPp = f.sPp,
+    *const sL = f.sL, *const sA = f.sA, *const sB = f.sB, *const sC = f.sC;
+  T* const sX = sC + MS;       // ... and the sweep's behind them: cross-covariance C_t
   T* const sPs = sX + MS;      // smoothed covariance Ps_t
   T* const sPm = sPs + MS;     // Ps_{t-1}
   T* const sM = sPm + MS;
@@ -74,199 +68,29 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   T* const sRi = sQi + MS;     // R^-1
   T* const sN = sRi + MS;
   T* const sV = sN + MS;
-  T* const vm = sV + MS;       // filtered mean
-  T* const vq = vm + MD;
-  T* const vr = vq + MD;
-  T* const vx = vr + MD;
-  T* const vmp = vx + MD;      // predicted mean
-  T* const vy = vmp + MD;      // innovation -> L^-1 y
-  T* const vzs = vy + MD;      // zbar_t
+  T *const vm = f.vm, *const vq = f.vq, *const vr = f.vr, *const vx = f.vx, *const vmp = f.vmp;
+  T* const vzs = f.vy + MD;    // zbar_t
   T* const vzp = vzs + MD;     // zbar_{t-1}
   T* const vd = vzp + MD;
   T* const ve = vd + MD;       // ebar
   T* const vu = ve + MD;       // ubar
-  T* const sc = vu + MD;       // scalars
 
-  const int lane = threadIdx.x;
-  const int64_t b = blockIdx.x;
-  const int h = a.h, o = a.o, Tn = a.T, hh = h * h, ho = h * o, oo = o * o;
+  const int h = a.m.h, o = a.m.o, Tn = a.m.T, hh = h * h, ho = h * o, oo = o * o;
   const T NaN = std::numeric_limits<T>::quiet_NaN();
-
-  // the elements this lane owns of an [h, h], [h, o] and [o, o] matrix: LDS offsets (-1: none)
-  int lhh[EPL], lho[EPL], loo[EPL];
-#pragma unroll
-  for (int k = 0; k < EPL; ++k) {
-    const int e = lane + 64 * k;
-    lhh[k] = e < hh ? (e / h) * LD + e % h : -1;
-    lho[k] = e < ho ? (e / o) * LD + e % o : -1;
-    loo[k] = e < oo ? (e / o) * LD + e % o : -1;
-  }
-
-  const T* m0b = (const T*)a.m0 + b * a.m0_sb;
-  const T* P0b = (const T*)a.P0 + b * a.P0_sb;
-  const T* Fb = (const T*)a.F + b * a.F_sb;
-  const T* qb = (const T*)a.q + b * a.q_sb;
-  const T* Qb = (const T*)a.Q + b * a.Q_sb;
-  const T* Hb = (const T*)a.H + b * a.H_sb;
-  const T* rb = (const T*)a.r + b * a.r_sb;
-  const T* Rb = (const T*)a.R + b * a.R_sb;
-  const T* xb = (const T*)a.x + b * (int64_t)Tn * o;
+  const auto& lhh = f.lhh;
+  const auto& lho = f.lho;
+  const auto& loo = f.loo;
+  bool& bad = f.bad;
   const int64_t wstep = h + hh;
   T* wsb = a.grads ? (T*)a.ws + b * (int64_t)Tn * wstep : nullptr;
 
-  // one step's inputs in registers: loaded a step ahead, written to LDS at the top of their step
-  T pF[EPL], pQ[EPL], pH[EPL], pR[EPL], pP[EPL], pq = T(0), pr = T(0), px = T(0), pm = T(0);
-#pragma unroll
-  for (int k = 0; k < EPL; ++k) pF[k] = pQ[k] = pH[k] = pR[k] = pP[k] = T(0);
-  auto load_params = [&](int t, bool first) {
-    if (first || a.F_ss) {
-      const T* p = Fb + (int64_t)t * a.F_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pF[k] = p[lane + 64 * k];
-    }
-    if (first || a.Q_ss) {
-      const T* p = Qb + (int64_t)t * a.Q_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pQ[k] = p[lane + 64 * k];
-    }
-    if (first || a.H_ss) {
-      const T* p = Hb + (int64_t)t * a.H_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lho[k] >= 0) pH[k] = p[lane + 64 * k];
-    }
-    if (first || a.R_ss) {
-      const T* p = Rb + (int64_t)t * a.R_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (loo[k] >= 0) pR[k] = p[lane + 64 * k];
-    }
-    if ((first || a.q_ss) && lane < h) pq = qb[(int64_t)t * a.q_ss + lane];
-    if ((first || a.r_ss) && lane < o) pr = rb[(int64_t)t * a.r_ss + lane];
-    if (lane < o) px = xb[(int64_t)t * o + lane];
-  };
-  auto commit_params = [&](bool first) {
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      if ((first || a.F_ss) && lhh[k] >= 0) sF[lhh[k]] = pF[k];
-      if ((first || a.Q_ss) && lhh[k] >= 0) sQ[lhh[k]] = pQ[k];
-      if ((first || a.H_ss) && lho[k] >= 0) sH[lho[k]] = pH[k];
-      if ((first || a.R_ss) && loo[k] >= 0) sR[loo[k]] = pR[k];
-    }
-    if ((first || a.q_ss) && lane < h) vq[lane] = pq;
-    if ((first || a.r_ss) && lane < o) vr[lane] = pr;
-    if (lane < o) vx[lane] = px;
-  };
-  // predicted moments from (vm, sP) and the step's parameters: vmp, sPp (symmetrised); leaves F^T P in sA and a
-  // copy of sPp in ``copy`` when given.  Ends with a barrier.
-  auto predict = [&](T* copy) {
-    if (lane < h) {
-      T s = vq[lane];
-      for (int i = 0; i < h; ++i) s += vm[i] * sF[i * LD + lane];
-      vmp[lane] = s;
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sF[i * LD + j] * sP[i * LD + c];
-        sA[lhh[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = sQ[lhh[k]];
-        for (int i = 0; i < h; ++i) s += sA[j * LD + i] * sF[i * LD + c];
-        sC[lhh[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        const T s = T(0.5) * (sC[j * LD + c] + sC[c * LD + j]);
-        sPp[lhh[k]] = s;
-        if (copy) copy[lhh[k]] = s;
-      }
-    __syncthreads();
-  };
-
   // ---- forward: the Kalman filter ----------------------------------------------------------------------------
-#pragma unroll
-  for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) sP[lhh[k]] = P0b[lane + 64 * k];
-  if (lane < h) vm[lane] = m0b[lane];
-  load_params(0, true);
+  f.start();
   double lp = 0.0;               // (in double also for float32: T terms of one sign, |log_prob| grows with T)
-  bool bad = false;
   const T half_log_2pi_o = T(0.91893853320467274178) * T(o);
   for (int t = 0; t < Tn; ++t) {
-    __syncthreads();
-    commit_params(t == 0);
-    if (t + 1 < Tn) load_params(t + 1, false);
-    __syncthreads();
-    predict(nullptr);
-    if (lane < o) {                                             // innovation
-      T s = vx[lane] - vr[lane];
-      for (int j = 0; j < h; ++j) s -= vmp[j] * sH[j * LD + lane];
-      vy[lane] = s;
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)                               // sB = P^p H
-      if (lho[k] >= 0) {
-        const int j = lho[k] / LD, c = lho[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sPp[j * LD + i] * sH[i * LD + c];
-        sB[lho[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)                               // S = H^T P^p H + R
-      if (loo[k] >= 0) {
-        const int r_ = loo[k] / LD, c = loo[k] % LD;
-        T s = sR[loo[k]];
-        for (int j = 0; j < h; ++j) s += sH[j * LD + r_] * sB[j * LD + c];
-        sL[loo[k]] = s;
-      }
-    __syncthreads();
-    const T logdet = gh_cholesky<T, MD>(sL, o, lane, bad);
-    if (lane < h) gh_forward_sub<T, LD>(sL, sB + lane * LD, 1, o);          // row j of U = P^p H L^-T
-    if (lane == h) sc[0] = gh_forward_sub<T, LD>(sL, vy, 1, o);             // v = L^-1 y, |v|^2
-    __syncthreads();
-    lp += (double)(T(-0.5) * sc[0] - logdet - half_log_2pi_o);
-    T nm = T(0);
-    if (lane < h) {
-      nm = vmp[lane];
-      for (int c = 0; c < o; ++c) nm += sB[lane * LD + c] * vy[c];
-    }
-    T nP[EPL];
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      nP[k] = T(0);
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = sPp[lhh[k]];
-        for (int i = 0; i < o; ++i) s -= sB[j * LD + i] * sB[c * LD + i];
-        nP[k] = s;
-      }
-    }
-    // (vm and sP are read by this phase only through vmp / sPp: no barrier before they are overwritten)
-    if (lane < h) vm[lane] = nm;
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sP[lhh[k]] = nP[k];
-    if (a.grads) {
-      T* w = wsb + (int64_t)t * wstep;
-      if (lane < h) w[lane] = nm;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) w[h + lane + 64 * k] = nP[k];
-    }
+    const T logdet = f.step(t, a.grads ? wsb + (int64_t)t * wstep : nullptr);
+    lp += (double)(T(-0.5) * f.sc[0] - logdet - half_log_2pi_o);
   }
   __syncthreads();
   if (lane == 0) ((T*)a.lp)[b] = bad ? NaN : (T)lp;
@@ -281,8 +105,8 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   // ---- backward: the Rauch-Tung-Striebel sweep and the expected complete-data score ---------------------------
   T* const gm0 = (T*)a.g_m0 + b * h;
   T* const gP0 = (T*)a.g_P0 + b * hh;
-  const int64_t TF = a.F_ss ? Tn : 1, Tq = a.q_ss ? Tn : 1, TQ = a.Q_ss ? Tn : 1, TH = a.H_ss ? Tn : 1,
-                Tr = a.r_ss ? Tn : 1, TR = a.R_ss ? Tn : 1;
+  const int64_t TF = a.m.F_ss ? Tn : 1, Tq = a.m.q_ss ? Tn : 1, TQ = a.m.Q_ss ? Tn : 1, TH = a.m.H_ss ? Tn : 1,
+                Tr = a.m.r_ss ? Tn : 1, TR = a.m.R_ss ? Tn : 1;
   T* const gF = (T*)a.g_F + b * TF * hh;
   T* const gq = (T*)a.g_q + b * Tq * h;
   T* const gQ = (T*)a.g_Q + b * TQ * hh;
@@ -340,8 +164,8 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   for (int k = 0; k < EPL; ++k)
     if (lhh[k] >= 0) sPs[lhh[k]] = sP[lhh[k]];
   __syncthreads();
-  if (!a.Q_ss) spd_inverse(sQ, sQi, h, lhh);
-  if (!a.R_ss) spd_inverse(sR, sRi, o, loo);
+  if (!a.m.Q_ss) spd_inverse(sQ, sQi, h, lhh);
+  if (!a.m.R_ss) spd_inverse(sR, sRi, o, loo);
 
   T aF[EPL], aQ[EPL], aH[EPL], aR[EPL], aq = T(0), ar = T(0);
 #pragma unroll
@@ -349,36 +173,36 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
 
   auto load_filtered = [&](int t) {          // (m_{t-1}, P_{t-1}) of 0-based step t
     if (t == 0) {
-      if (lane < h) pm = m0b[lane];
+      if (lane < h) f.pm = f.m0b[lane];
 #pragma unroll
       for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pP[k] = P0b[lane + 64 * k];
+        if (lhh[k] >= 0) f.pP[k] = f.P0b[lane + 64 * k];
     } else {
       const T* w = wsb + (int64_t)(t - 1) * wstep;
-      if (lane < h) pm = w[lane];
+      if (lane < h) f.pm = w[lane];
 #pragma unroll
       for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pP[k] = w[h + lane + 64 * k];
+        if (lhh[k] >= 0) f.pP[k] = w[h + lane + 64 * k];
     }
   };
   // (the forward pass wrote the workspace with the lanes that read it back here: same lane, same address)
-  load_params(Tn - 1, false);
+  f.load_params(Tn - 1, false, true);
   load_filtered(Tn - 1);
   for (int t = Tn - 1; t >= 0; --t) {
     __syncthreads();
-    commit_params(false);
-    if (lane < h) vm[lane] = pm;
+    f.commit_params(false, true);
+    if (lane < h) vm[lane] = f.pm;
 #pragma unroll
     for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sP[lhh[k]] = pP[k];
+      if (lhh[k] >= 0) sP[lhh[k]] = f.pP[k];
     if (t > 0) {
-      load_params(t - 1, false);
+      f.load_params(t - 1, false, true);
       load_filtered(t - 1);
     }
     __syncthreads();
-    if (a.Q_ss) spd_inverse(sQ, sQi, h, lhh);
-    if (a.R_ss) spd_inverse(sR, sRi, o, loo);
-    predict(sL);                                                 // vmp, sPp (= sL), sA = F^T P_{t-1}
+    if (a.m.Q_ss) spd_inverse(sQ, sQi, h, lhh);
+    if (a.m.R_ss) spd_inverse(sR, sRi, o, loo);
+    f.predict(sL);                                                 // vmp, sPp (= sL), sA = F^T P_{t-1}
     gh_cholesky<T, MD>(sL, h, lane, bad);
     if (lane < h) {                                              // column i of sA <- (P^p)^-1 column: sA[j, i] = G[i, j]
       gh_forward_sub<T, LD>(sL, sA + lane, LD, h);
@@ -477,12 +301,12 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
     if (lane < h) {                                              // d/dq = Q^-1 ebar
       T s = T(0);
       for (int c = 0; c < h; ++c) s += sQi[lane * LD + c] * ve[c];
-      if (a.q_ss) gq[(int64_t)t * h + lane] = s; else aq += s;
+      if (a.m.q_ss) gq[(int64_t)t * h + lane] = s; else aq += s;
     }
     if (lane < o) {                                              // d/dr = R^-1 ubar = -d/dx
       T s = T(0);
       for (int c = 0; c < o; ++c) s += sRi[lane * LD + c] * vu[c];
-      if (a.r_ss) gr[(int64_t)t * o + lane] = s; else ar += s;
+      if (a.m.r_ss) gr[(int64_t)t * o + lane] = s; else ar += s;
       gx[(int64_t)t * o + lane] = -s;
     }
 #pragma unroll
@@ -495,14 +319,14 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
           s += sC[j * LD + i] * sQi[i * LD + c];                 // d/dF = (...) Q^-1
           s2 += sQi[j * LD + i] * sE[i * LD + c];                // sM = Q^-1 E
         }
-        if (a.F_ss) gF[(int64_t)t * hh + e] = s; else aF[k] += s;
+        if (a.m.F_ss) gF[(int64_t)t * hh + e] = s; else aF[k] += s;
         sM[lhh[k]] = s2;
       }
       if (lho[k] >= 0) {                                         // d/dH = (...) R^-1
         const int j = lho[k] / LD, c = lho[k] % LD;
         T s = T(0);
         for (int i = 0; i < o; ++i) s += sB[j * LD + i] * sRi[i * LD + c];
-        if (a.H_ss) gH[(int64_t)t * ho + e] = s; else aH[k] += s;
+        if (a.m.H_ss) gH[(int64_t)t * ho + e] = s; else aH[k] += s;
       }
       if (loo[k] >= 0) {                                         // sPp = R^-1 V
         const int r_ = loo[k] / LD, c = loo[k] % LD;
@@ -520,7 +344,7 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
         T s = T(0);
         for (int i = 0; i < h; ++i) s += sM[j * LD + i] * sQi[i * LD + c];
         s *= T(0.5);
-        if (a.Q_ss) gQ[(int64_t)t * hh + e] = s; else aQ[k] += s;
+        if (a.m.Q_ss) gQ[(int64_t)t * hh + e] = s; else aQ[k] += s;
         sPs[lhh[k]] = sPm[lhh[k]];                               // (Ps_t was last read before the barrier above)
       }
       if (loo[k] >= 0) {                                         // d/dR = R^-1 V R^-1 / 2
@@ -528,24 +352,24 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
         T s = T(0);
         for (int i = 0; i < o; ++i) s += sPp[r_ * LD + i] * sRi[i * LD + c];
         s *= T(0.5);
-        if (a.R_ss) gR[(int64_t)t * oo + e] = s; else aR[k] += s;
+        if (a.m.R_ss) gR[(int64_t)t * oo + e] = s; else aR[k] += s;
       }
     }
     if (lane < h) vzs[lane] = vzp[lane];
   }
   __syncthreads();
   // the step-summed gradients of the time-homogeneous parameters
-  if (!a.q_ss && lane < h) gq[lane] = aq;
-  if (!a.r_ss && lane < o) gr[lane] = ar;
+  if (!a.m.q_ss && lane < h) gq[lane] = aq;
+  if (!a.m.r_ss && lane < o) gr[lane] = ar;
 #pragma unroll
   for (int k = 0; k < EPL; ++k) {
     const int e = lane + 64 * k;
     if (lhh[k] >= 0) {
-      if (!a.F_ss) gF[e] = aF[k];
-      if (!a.Q_ss) gQ[e] = aQ[k];
+      if (!a.m.F_ss) gF[e] = aF[k];
+      if (!a.m.Q_ss) gQ[e] = aQ[k];
     }
-    if (lho[k] >= 0 && !a.H_ss) gH[e] = aH[k];
-    if (loo[k] >= 0 && !a.R_ss) gR[e] = aR[k];
+    if (lho[k] >= 0 && !a.m.H_ss) gH[e] = aH[k];
+    if (loo[k] >= 0 && !a.m.R_ss) gR[e] = aR[k];
   }
   // the initial state: (vm, sP) hold (m0, P0) since step 1 of the sweep, (vzs, sPs) = (zbar_0, Ps_0)
   spd_inverse(sP, sQi, h, lhh);
@@ -624,11 +448,11 @@ int pa_gaussian_hmm_fwd_bwd(int dtype, const void* m0, int64_t m0_stride_batch, 
              "gaussian_hmm: negative stride");
   const size_t need = pa_gaussian_hmm_workspace(dtype, B, T, hidden, obs, ng != 0);
   PA_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "gaussian_hmm: workspace too small");
-  pa::GhmmArgs a{m0, P0, F, q, Q, H, r, R, x,
-                 m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
-                 Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
-                 R_stride_batch, R_stride_step,
-                 (int)T, (int)hidden, (int)obs, ng != 0,
+  pa::GhmmArgs a{{m0, P0, F, q, Q, H, r, R, x,
+                  m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
+                  Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
+                  R_stride_batch, R_stride_step, (int)T, (int)hidden, (int)obs},
+                 ng != 0,
                  log_prob, filter_mean, filter_cov, grad_m0, grad_P0, grad_F, grad_q, grad_Q, grad_H, grad_r, grad_R,
                  grad_x, workspace};
   hipStream_t s = pa::as_stream(stream);

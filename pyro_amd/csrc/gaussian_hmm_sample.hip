@@ -10,10 +10,10 @@
 //     z_T = c_T + L_T eps_T,     z_{t-1} = c_{t-1} + G_{t-1} z_t + L_{t-1} eps_{t-1},   t = T..2
 // whose "maps" (c_t, G_t, L_t) depend on the series only, not on the draw (G_T = 0; z_0 is not drawn).
 //
-// Maps kernel, one wave per series.  Forward: the Kalman filter of gaussian_hmm_kernel, operation for operation (P^p
-// symmetrised, S = L L^T, U = P^p H L^-T, P = P^p - U U^T, a non-positive pivot of S marks the series), keeping
-// (m_t, P_t) of every step in the workspace.  Backward: L_T = chol(sym(P_T)), c_T = m_T, and for t = T..2 from
-// (m_{t-1}, P_{t-1}) and step t's F, q, Q: m^p, P^p as in the forward pass,
+// Maps kernel, one wave per series.  Forward: the filter of gaussian_hmm.h (GhFilter, shared with gaussian_hmm_kernel;
+// a non-positive pivot of S marks the series), keeping (m_t, P_t) of every step in the workspace.  Backward:
+// L_T = chol(sym(P_T)), c_T = m_T, and for t = T..2 from (m_{t-1}, P_{t-1}) and step t's F, q, Q: m^p, P^p as in the
+// forward pass,
 //     G = P_{t-1} F (P^p)^-1,   J = I - G F^T,   C = sym(J P_{t-1} J^T + G Q G^T),   L_{t-1} = chol(C),
 //     c_{t-1} = m_{t-1} - G m^p.
 // C is the conditional covariance in JOSEPH form: a sum of two positive semi-definite terms.  The shorter
@@ -27,15 +27,12 @@
 // registers while the current step computes, one barrier per step), every lane reads its eps[s, b, t, :] a step
 // ahead and writes z[s, b, t, :], both laid out [S, B, T, hidden].
 //
-// The maps kernel's LDS layout and lane ownership are those of gaussian_hmm_kernel (row stride MD + 1, MD^2 / 64
-// elements of every product per lane).
-//
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage), one wave of 64 lanes per block:
 //     kernel   instantiation    VGPRs  SGPRs  scratch   LDS bytes   waves / SIMD
 //     maps     <float , 8>      71     106    0         3656        7
-//     maps     <float , 16>     156    106    0         13448       3
+//     maps     <float , 16>     160    106    0         13448       3
 //     maps     <double, 8>      95     106    0         7312        5
-//     maps     <double, 16>     208    106    0         26896       2
+//     maps     <double, 16>     204    106    0         26896       2
 //     paths    <float , 8>      60     56     0         1088        8
 //     paths    <float , 16>     96     96     0         4224        5
 //     paths    <double, 8>      95     56     0         2176        5
@@ -48,9 +45,7 @@
 namespace pa {
 
 struct GhsArgs {
-  const void *m0, *P0, *F, *q, *Q, *H, *r, *R, *x;
-  int64_t m0_sb, P0_sb, F_sb, F_ss, q_sb, q_ss, Q_sb, Q_ss, H_sb, H_ss, r_sb, r_ss, R_sb, R_ss;
-  int T, h, o;
+  GhModel m;
   void *ws, *c, *G, *L;
 };
 
@@ -59,139 +54,25 @@ __global__ __launch_bounds__(64) void gaussian_hmm_maps_kernel(const GhsArgs a) 
   constexpr int LD = MD + 1, MS = MD * LD, EPL = MD * MD / 64;
   constexpr int NMAT = 12, NVEC = 6;
   __shared__ T sm[NMAT * MS + NVEC * MD + 2];
-  T* const sP = sm;            // filtered covariance P_t (backward: P_{t-1})
-  T* const sF = sP + MS;
-  T* const sQ = sF + MS;
-  T* const sH = sQ + MS;
-  T* const sR = sH + MS;
-  T* const sPp = sR + MS;      // predicted covariance
-  T* const sL = sPp + MS;      // Cholesky factors
-  T* const sA = sL + MS;       // F^T P; backward: G^T
-  T* const sB = sA + MS;       // P^p H -> U; backward: G Q
-  T* const sC = sB + MS;       // backward: J P_{t-1}
-  T* const sJ = sC + MS;       // I - G F^T
-  T* const sD = sJ + MS;       // the conditional covariance before it is symmetrised
-  T* const vm = sD + MS;       // filtered mean
-  T* const vq = vm + MD;
-  T* const vr = vq + MD;
-  T* const vx = vr + MD;
-  T* const vmp = vx + MD;      // predicted mean
-  T* const vy = vmp + MD;      // innovation -> L^-1 y
-  T* const sc = vy + MD;       // scalars
-
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
-  const int h = a.h, o = a.o, Tn = a.T, hh = h * h, ho = h * o, oo = o * o;
+  GhFilter<T, MD> f(a.m, sm, sm + NMAT * MS, sm + NMAT * MS + NVEC * MD, lane, b);
+  // the filter's matrices (backward: sP = P_{t-1}, sA = G^T, sB = G Q, sC = J P_{t-1}) and the sweep's behind them
+  T *const sP = f.sP, *const sF = f.sF, *const sQ = f.sQ, *const sL = f.sL, *const sA = f.sA, *const sB = f.sB,
+    *const sC = f.sC, *const vm = f.vm, *const vmp = f.vmp;
+  T* const sJ = sC + MS;       // I - G F^T
+  T* const sD = sJ + MS;       // the conditional covariance before it is symmetrised
+
+  const int h = a.m.h, Tn = a.m.T, hh = h * h;
   const T NaN = std::numeric_limits<T>::quiet_NaN();
-
-  // the elements this lane owns of an [h, h], [h, o] and [o, o] matrix: LDS offsets (-1: none)
-  int lhh[EPL], lho[EPL], loo[EPL];
-#pragma unroll
-  for (int k = 0; k < EPL; ++k) {
-    const int e = lane + 64 * k;
-    lhh[k] = e < hh ? (e / h) * LD + e % h : -1;
-    lho[k] = e < ho ? (e / o) * LD + e % o : -1;
-    loo[k] = e < oo ? (e / o) * LD + e % o : -1;
-  }
-
-  const T* m0b = (const T*)a.m0 + b * a.m0_sb;
-  const T* P0b = (const T*)a.P0 + b * a.P0_sb;
-  const T* Fb = (const T*)a.F + b * a.F_sb;
-  const T* qb = (const T*)a.q + b * a.q_sb;
-  const T* Qb = (const T*)a.Q + b * a.Q_sb;
-  const T* Hb = (const T*)a.H + b * a.H_sb;
-  const T* rb = (const T*)a.r + b * a.r_sb;
-  const T* Rb = (const T*)a.R + b * a.R_sb;
-  const T* xb = (const T*)a.x + b * (int64_t)Tn * o;
+  const auto& lhh = f.lhh;
+  bool& bad = f.bad;
   const int64_t wstep = h + hh;
   T* const wsb = (T*)a.ws + b * (int64_t)Tn * wstep;
   T* const cb = (T*)a.c + b * (int64_t)Tn * h;
   T* const Gb = (T*)a.G + b * (int64_t)Tn * hh;
   T* const Lb = (T*)a.L + b * (int64_t)Tn * hh;
 
-  // one step's inputs in registers: loaded a step ahead, written to LDS at the top of their step
-  T pF[EPL], pQ[EPL], pH[EPL], pR[EPL], pP[EPL], pq = T(0), pr = T(0), px = T(0), pm = T(0);
-#pragma unroll
-  for (int k = 0; k < EPL; ++k) pF[k] = pQ[k] = pH[k] = pR[k] = pP[k] = T(0);
-  // (``obs``: the observation side and the data too -- the forward pass; the backward sweep reads F, q, Q only)
-  auto load_params = [&](int t, bool first, bool obs) {
-    if (first || a.F_ss) {
-      const T* p = Fb + (int64_t)t * a.F_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pF[k] = p[lane + 64 * k];
-    }
-    if (first || a.Q_ss) {
-      const T* p = Qb + (int64_t)t * a.Q_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lhh[k] >= 0) pQ[k] = p[lane + 64 * k];
-    }
-    if ((first || a.q_ss) && lane < h) pq = qb[(int64_t)t * a.q_ss + lane];
-    if (!obs) return;
-    if (first || a.H_ss) {
-      const T* p = Hb + (int64_t)t * a.H_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (lho[k] >= 0) pH[k] = p[lane + 64 * k];
-    }
-    if (first || a.R_ss) {
-      const T* p = Rb + (int64_t)t * a.R_ss;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (loo[k] >= 0) pR[k] = p[lane + 64 * k];
-    }
-    if ((first || a.r_ss) && lane < o) pr = rb[(int64_t)t * a.r_ss + lane];
-    if (lane < o) px = xb[(int64_t)t * o + lane];
-  };
-  auto commit_params = [&](bool first, bool obs) {
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      if ((first || a.F_ss) && lhh[k] >= 0) sF[lhh[k]] = pF[k];
-      if ((first || a.Q_ss) && lhh[k] >= 0) sQ[lhh[k]] = pQ[k];
-      if (obs && (first || a.H_ss) && lho[k] >= 0) sH[lho[k]] = pH[k];
-      if (obs && (first || a.R_ss) && loo[k] >= 0) sR[loo[k]] = pR[k];
-    }
-    if ((first || a.q_ss) && lane < h) vq[lane] = pq;
-    if (obs && (first || a.r_ss) && lane < o) vr[lane] = pr;
-    if (obs && lane < o) vx[lane] = px;
-  };
-  // predicted moments from (vm, sP) and the step's parameters: vmp, sPp (symmetrised); leaves F^T P in sA and a
-  // copy of sPp in ``copy`` when given.  Ends with a barrier.
-  auto predict = [&](T* copy) {
-    if (lane < h) {
-      T s = vq[lane];
-      for (int i = 0; i < h; ++i) s += vm[i] * sF[i * LD + lane];
-      vmp[lane] = s;
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sF[i * LD + j] * sP[i * LD + c];
-        sA[lhh[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = sQ[lhh[k]];
-        for (int i = 0; i < h; ++i) s += sA[j * LD + i] * sF[i * LD + c];
-        sC[lhh[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        const T s = T(0.5) * (sC[j * LD + c] + sC[c * LD + j]);
-        sPp[lhh[k]] = s;
-        if (copy) copy[lhh[k]] = s;
-      }
-    __syncthreads();
-  };
   // every element of the maps is written by ONE lane (element e of a matrix by lane e % 64, a vector's by lane e):
   // the NaN fill of a marked series comes after that lane's own stores in program order
   auto fill_nan = [&]() {
@@ -204,72 +85,8 @@ __global__ __launch_bounds__(64) void gaussian_hmm_maps_kernel(const GhsArgs a) 
   };
 
   // ---- forward: the Kalman filter, every step's (m_t, P_t) kept --------------------------------------------------
-#pragma unroll
-  for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) sP[lhh[k]] = P0b[lane + 64 * k];
-  if (lane < h) vm[lane] = m0b[lane];
-  load_params(0, true, true);
-  bool bad = false;
-  for (int t = 0; t < Tn; ++t) {
-    __syncthreads();
-    commit_params(t == 0, true);
-    if (t + 1 < Tn) load_params(t + 1, false, true);
-    __syncthreads();
-    predict(nullptr);
-    if (lane < o) {                                             // innovation
-      T s = vx[lane] - vr[lane];
-      for (int j = 0; j < h; ++j) s -= vmp[j] * sH[j * LD + lane];
-      vy[lane] = s;
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)                               // sB = P^p H
-      if (lho[k] >= 0) {
-        const int j = lho[k] / LD, c = lho[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sPp[j * LD + i] * sH[i * LD + c];
-        sB[lho[k]] = s;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)                               // S = H^T P^p H + R
-      if (loo[k] >= 0) {
-        const int r_ = loo[k] / LD, c = loo[k] % LD;
-        T s = sR[loo[k]];
-        for (int j = 0; j < h; ++j) s += sH[j * LD + r_] * sB[j * LD + c];
-        sL[loo[k]] = s;
-      }
-    __syncthreads();
-    gh_cholesky<T, MD>(sL, o, lane, bad);
-    if (lane < h) gh_forward_sub<T, LD>(sL, sB + lane * LD, 1, o);          // row j of U = P^p H L^-T
-    if (lane == h) sc[0] = gh_forward_sub<T, LD>(sL, vy, 1, o);             // v = L^-1 y
-    __syncthreads();
-    T nm = T(0);
-    if (lane < h) {
-      nm = vmp[lane];
-      for (int c = 0; c < o; ++c) nm += sB[lane * LD + c] * vy[c];
-    }
-    T nP[EPL];
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      nP[k] = T(0);
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = sPp[lhh[k]];
-        for (int i = 0; i < o; ++i) s -= sB[j * LD + i] * sB[c * LD + i];
-        nP[k] = s;
-      }
-    }
-    // (vm and sP are read by this phase only through vmp / sPp: no barrier before they are overwritten)
-    if (lane < h) vm[lane] = nm;
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sP[lhh[k]] = nP[k];
-    T* w = wsb + (int64_t)t * wstep;
-    if (lane < h) w[lane] = nm;
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) w[h + lane + 64 * k] = nP[k];
-  }
+  f.start();
+  for (int t = 0; t < Tn; ++t) f.step(t, wsb + (int64_t)t * wstep);
   __syncthreads();
   if (bad) {
     fill_nan();
@@ -300,29 +117,29 @@ __global__ __launch_bounds__(64) void gaussian_hmm_maps_kernel(const GhsArgs a) 
 
   auto load_filtered = [&](int t) {          // (m_t, P_t) of 0-based step t
     const T* w = wsb + (int64_t)t * wstep;
-    if (lane < h) pm = w[lane];
+    if (lane < h) f.pm = w[lane];
 #pragma unroll
     for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) pP[k] = w[h + lane + 64 * k];
+      if (lhh[k] >= 0) f.pP[k] = w[h + lane + 64 * k];
   };
   // (the forward pass wrote the workspace with the lanes that read it back here: same lane, same address)
   if (Tn > 1) {
-    load_params(Tn - 1, false, false);
+    f.load_params(Tn - 1, false, false);
     load_filtered(Tn - 2);
   }
   for (int t = Tn - 1; t >= 1; --t) {        // step t's transition, the filtered moments of step t - 1 -> map t - 1
     __syncthreads();
-    commit_params(false, false);
-    if (lane < h) vm[lane] = pm;
+    f.commit_params(false, false);
+    if (lane < h) vm[lane] = f.pm;
 #pragma unroll
     for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sP[lhh[k]] = pP[k];
+      if (lhh[k] >= 0) sP[lhh[k]] = f.pP[k];
     if (t > 1) {
-      load_params(t - 1, false, false);
+      f.load_params(t - 1, false, false);
       load_filtered(t - 2);
     }
     __syncthreads();
-    predict(sL);                                                 // vmp, sPp (= sL), sA = F^T P_{t-1}
+    f.predict(sL);                                                 // vmp, sPp (= sL), sA = F^T P_{t-1}
     gh_cholesky<T, MD>(sL, h, lane, bad);
     if (lane < h) {                                              // column i of sA <- (P^p)^-1 column: sA[j, i] = G[i, j]
       gh_forward_sub<T, LD>(sL, sA + lane, LD, h);
@@ -521,11 +338,11 @@ int pa_gaussian_hmm_sample(int dtype, const void* m0, int64_t m0_stride_batch, c
     maps_G = w + (size_t)(BT * hidden) * el;
     maps_L = w + (size_t)(BT * (hidden + hh)) * el;
   }
-  pa::GhsArgs a{m0, P0, F, q, Q, H, r, R, x,
-                m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
-                Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
-                R_stride_batch, R_stride_step,
-                (int)T, (int)hidden, (int)obs, workspace, maps_c, maps_G, maps_L};
+  pa::GhsArgs a{{m0, P0, F, q, Q, H, r, R, x,
+                 m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
+                 Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
+                 R_stride_batch, R_stride_step, (int)T, (int)hidden, (int)obs},
+                workspace, maps_c, maps_G, maps_L};
   hipStream_t st = pa::as_stream(stream);
   const bool small = hidden <= 8 && obs <= 8;
 #define PA_GHS_MAPS(T_, MD_) \

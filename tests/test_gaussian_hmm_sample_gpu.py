@@ -241,6 +241,26 @@ def test_near_singular_process_noise_float32(gpu):
     assert err["draws"] <= 4 * base["draws"], (err, base)
 
 
+@pytest.mark.parametrize("case", ["b3_t1_h2_o1", "b2_t9_h4_o3_het", "b2_t40_h16_o16", "b2_t17_h5_o16_het"])
+@pytest.mark.parametrize("dtype", [F32, F64])
+def test_both_kernels_run_the_same_filter(case, dtype, gpu):
+    """The maps kernel and gaussian_hmm_kernel share one filter (csrc/gaussian_hmm.h): the maps kernel's c_T is its
+    filtered m_T stored untouched, so it equals the other kernel's filter mean BIT FOR BIT, and L_T L_T^T is
+    sym(P_T) of that kernel up to the Cholesky's rounding (float64: 1e-9; float32: the file's rule, four times the
+    ``cov`` error of the float32 torch route on the case).  T = 1, per-step parameters, both padded widths, and
+    hidden != obs with the width chosen by obs: all four instantiations of both kernels."""
+    raw, eps = _raw(case, dtype, gpu)
+    _, (fm, fP), _ = kernels.gaussian_hmm_fwd_bwd(*raw, need_grads=False, need_filter=True)
+    _, (c, _G, L) = kernels.gaussian_hmm_sample(*raw, eps[:0].contiguous(), need_maps=True)
+    assert torch.isfinite(fm).all() and torch.equal(c[:, -1], fm)
+    LT = L[:, -1].double().cpu()
+    want = fP.double().cpu()
+    err = gc.rel_err((LT @ LT.transpose(-1, -2)).numpy(), (0.5 * (want + want.transpose(-1, -2))).numpy())
+    tol = TOL64 if dtype == F64 else 4 * _torch_f32_errors(case)["cov"]
+    print(case, dtype, "L_T L_T^T against sym(P_T): %.1e, allowed %.1e" % (err, tol))
+    assert err <= tol, (err, tol)
+
+
 @pytest.mark.parametrize("dtype", [F32, F64])
 def test_sample_chunk_edges(dtype, gpu):
     """one lane per draw, 64 draws per block: a draw does not depend on S, on its lane or on the other series"""
