@@ -957,6 +957,35 @@ int pa_gaussian_hmm_sample(int dtype, const void* m0, int64_t m0_stride_batch, c
                            int64_t T, int64_t hidden, int64_t obs, int64_t S, const void* eps, void* z, void* maps_c,
                            void* maps_G, void* maps_L, void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gaussian_hmm_draw.hip: forward draws of that model, sample paths of x (and z) from the prior ------------
+ * Replaces GaussianHMM.rsample (pyro/distributions/hmm.py:584-594 over sequential_gaussian_filter_sample,
+ * pyro/ops/gaussian.py:600, then Gaussian.left_condition(z).rsample(): the parallel-scan filter with its tape and as
+ * many rounds of conditional draws, then a batched Cholesky for the observation noise) with two launches on the
+ * caller's stream.  Parameters and strides as for pa_gaussian_hmm_fwd_bwd; there is no data.
+ *   z_0 = m0 + L_0 e_0,   z_t = z_{t-1} F_t + q_t + L_{Q,t} e_t,   x_t = z_t H_t + r_t + L_{R,t} e'_t,   t = 1..T
+ * with L L^T the Cholesky factors of P0, Q_t, R_t (lower triangles read), each acting on its noise as L e.
+ * Launch 1, one wave per DISTINCT matrix: P0 per sequence (once with batch stride 0), Q and R per sequence and per
+ *   step along the axes whose stride is not 0; factors and one flag per factor go to the workspace.
+ * Launch 2, one lane per draw: x[s, b, t, :] and, when z is not NULL, z[s, b, t, :] from the standard normal
+ *   eps0 [S, B, hidden], eps_z [S, B, T, hidden], eps_x [S, B, T, obs]; x [S, B, T, obs], z [S, B, T, hidden], all
+ *   contiguous (noise of zeros gives the mean path).  z_0 is not written.
+ * A sequence one of whose factors (its own or a shared parameter's) has a non-positive pivot gets NaN for all of x
+ * and z; other sequences are untouched.  No atomics: bit-reproducible, and a draw depends neither on S nor on the
+ * other sequences.  hidden or obs > 16: PA_ERR_UNSUPPORTED.  B = 0 or S = 0: PA_OK without a launch.
+ * workspace: pa_gaussian_hmm_draw_workspace(...) bytes -- B hidden^2 + B T (hidden^2 + obs^2) elements of factors
+ * and B + 2 B T ints of flags, the need of per-sequence, per-step covariances.  The call itself asks only for the
+ * factors its strides make distinct, so pa_gaussian_hmm_draw_workspace(dtype, B', T', ...) suffices with B' = 1 when
+ * P0, Q and R all have batch stride 0 and T' = 1 when Q and R both have step stride 0. */
+size_t pa_gaussian_hmm_draw_workspace(int dtype, int64_t B, int64_t T, int64_t hidden, int64_t obs);
+int pa_gaussian_hmm_draw(int dtype, const void* m0, int64_t m0_stride_batch, const void* P0, int64_t P0_stride_batch,
+                         const void* F, int64_t F_stride_batch, int64_t F_stride_step, const void* q,
+                         int64_t q_stride_batch, int64_t q_stride_step, const void* Q, int64_t Q_stride_batch,
+                         int64_t Q_stride_step, const void* H, int64_t H_stride_batch, int64_t H_stride_step,
+                         const void* r, int64_t r_stride_batch, int64_t r_stride_step, const void* R,
+                         int64_t R_stride_batch, int64_t R_stride_step, int64_t B, int64_t T, int64_t hidden,
+                         int64_t obs, int64_t S, const void* eps0, const void* eps_z, const void* eps_x, void* x,
+                         void* z, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

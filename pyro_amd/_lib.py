@@ -333,6 +333,12 @@ _SIGNATURES = {
                                + [c_void_p, c_int64, c_int64, c_int64, c_int64]                   # x, B T hidden obs
                                + [c_int64, c_void_p, c_void_p] + [c_void_p] * 3                   # S eps z, the maps
                                + [c_void_p, c_size_t, c_void_p]),
+    "pa_gaussian_hmm_draw_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64]),
+    "pa_gaussian_hmm_draw": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64]                 # m0, P0
+                             + [c_void_p, c_int64, c_int64] * 6                                   # F q Q H r R
+                             + [c_int64] * 5 + [c_void_p] * 3                                     # B T hidden obs S, noise
+                             + [c_void_p, c_void_p]                                               # x, z
+                             + [c_void_p, c_size_t, c_void_p]),
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -390,12 +390,15 @@ struct GhmmLayout {
   int dt;
   int64_t B, T, h, o, sb[8], ss[8], steps[8];
 };
-GhmmLayout gaussian_hmm_layout(const at::Tensor* const* p, const at::Tensor& x) {
+// (``like``: the tensor whose dtype the parameters share -- the data, or the noise of an entry point without data)
+GhmmLayout gaussian_hmm_param_layout(const at::Tensor* const* p, const at::Tensor& like, int64_t B_, int64_t T_,
+                                     int64_t o_) {
   GhmmLayout l;
-  l.dt = dtype_of(x, "gaussian_hmm");
+  l.dt = dtype_of(like, "gaussian_hmm");
+  const at::Tensor& x = like;
   const at::Tensor& m0 = *p[0];
-  TORCH_CHECK(x.dim() == 3 && x.is_contiguous() && m0.dim() == 2, "pyro_amd::gaussian_hmm: x [B, T, obs] contiguous, m0 [B | 1, hidden]");
-  const int64_t B = l.B = x.size(0), T = l.T = x.size(1), o = l.o = x.size(2), h = l.h = m0.size(1);
+  TORCH_CHECK(m0.dim() == 2, "pyro_amd::gaussian_hmm: m0 [B | 1, hidden]");
+  const int64_t B = l.B = B_, T = l.T = T_, o = l.o = o_, h = l.h = m0.size(1);
   const std::vector<int64_t> ev[8] = {{h}, {h, h}, {h, h}, {h}, {h, h}, {h, o}, {o}, {o, o}};
   int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss, (&steps)[8] = l.steps;
   for (int i = 0; i < 8; ++i) {
@@ -415,6 +418,10 @@ GhmmLayout gaussian_hmm_layout(const at::Tensor* const* p, const at::Tensor& x) 
     ss[i] = steps[i] == 1 ? 0 : n;
   }
   return l;
+}
+GhmmLayout gaussian_hmm_layout(const at::Tensor* const* p, const at::Tensor& x) {
+  TORCH_CHECK(x.dim() == 3 && x.is_contiguous(), "pyro_amd::gaussian_hmm: x [B, T, obs] contiguous, m0 [B | 1, hidden]");
+  return gaussian_hmm_param_layout(p, x, x.size(0), x.size(1), x.size(2));
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian_hmm(
@@ -478,6 +485,45 @@ std::tuple<at::Tensor, std::vector<at::Tensor>> gaussian_hmm_sample(
                                ws.data_ptr(), ws_bytes, current_stream()),
         "gaussian_hmm_sample");
   return {z, maps};
+}
+
+// forward draws of that model in two launches (pyro/distributions/hmm.py:584-594 GaussianHMM.rsample over
+// pyro/ops/gaussian.py:600 sequential_gaussian_filter_sample and Gaussian.left_condition(z).rsample()).  Layouts as
+// kernels.gaussian_hmm_draw: the parameters as above, T steps, the standard normal eps0 [S, B, h], eps_z [S, B, T, h],
+// eps_x [S, B, T, o] -> x [S, B, T, o] and, with need_states, [z [S, B, T, h]] (empty without)
+std::tuple<at::Tensor, std::vector<at::Tensor>> gaussian_hmm_draw(
+    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
+    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov, int64_t T,
+    const at::Tensor& eps0, const at::Tensor& eps_z, const at::Tensor& eps_x, bool need_states) {
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  TORCH_CHECK(eps0.is_cuda() && eps0.dim() == 3 && eps0.is_contiguous() && obs.dim() == 4 && T >= 1,
+              "pyro_amd::gaussian_hmm_draw: eps0 [S, B, hidden] contiguous, obs [B | 1, T | 1, hidden, obs], T >= 1");
+  const int64_t S = eps0.size(0), B = eps0.size(1), o = obs.size(3);
+  const GhmmLayout l = gaussian_hmm_param_layout(p, eps0, B, T, o);
+  const int64_t h = l.h;
+  const int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss;
+  auto noise_ok = [&](const at::Tensor& e, int64_t n) {
+    return e.is_cuda() && e.scalar_type() == eps0.scalar_type() && e.is_contiguous() && e.dim() == 4 &&
+           e.size(0) == S && e.size(1) == B && e.size(2) == T && e.size(3) == n;
+  };
+  TORCH_CHECK(eps0.size(2) == h && noise_ok(eps_z, h) && noise_ok(eps_x, o),
+              "pyro_amd::gaussian_hmm_draw: eps0 [S, B, hidden], eps_z [S, B, T, hidden], eps_x [S, B, T, obs] "
+              "contiguous of the parameters' dtype");
+  const auto opt = eps0.options();
+  at::Tensor x = at::empty({S, B, T, o}, opt);
+  std::vector<at::Tensor> states;
+  if (need_states) states = {at::empty({S, B, T, h}, opt)};
+  // (only the factors the strides make distinct: see include/pyro_amd.h)
+  const int64_t Bw = (sb[1] || sb[4] || sb[7]) ? B : 1, Tw = (ss[4] || ss[7]) ? T : 1;
+  const size_t ws_bytes = pa_gaussian_hmm_draw_workspace(l.dt, Bw, Tw, h, o);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, opt.dtype(at::kByte));
+  check(pa_gaussian_hmm_draw(l.dt, m0.data_ptr(), sb[0], P0.data_ptr(), sb[1], trans.data_ptr(), sb[2], ss[2],
+                             trans_loc.data_ptr(), sb[3], ss[3], trans_cov.data_ptr(), sb[4], ss[4], obs.data_ptr(),
+                             sb[5], ss[5], obs_loc.data_ptr(), sb[6], ss[6], obs_cov.data_ptr(), sb[7], ss[7], B, T, h,
+                             o, S, eps0.data_ptr(), eps_z.data_ptr(), eps_x.data_ptr(), x.data_ptr(),
+                             need_states ? states[0].data_ptr() : nullptr, ws.data_ptr(), ws_bytes, current_stream()),
+        "gaussian_hmm_draw");
+  return {x, states};
 }
 
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
@@ -659,6 +705,9 @@ TORCH_LIBRARY(pyro_amd, m) {
         "Tensor filter_cov, Tensor[] grads)");
   m.def("gaussian_hmm_sample(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, Tensor x, Tensor eps, bool need_maps) -> (Tensor z, Tensor[] maps)");
+  m.def("gaussian_hmm_draw(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
+        "Tensor obs_loc, Tensor obs_cov, int T, Tensor eps0, Tensor eps_z, Tensor eps_x, bool need_states) -> "
+        "(Tensor x, Tensor[] states)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -689,6 +738,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("logchain_decode", &logchain_decode);
   m.impl("gaussian_hmm", &gaussian_hmm);
   m.impl("gaussian_hmm_sample", &gaussian_hmm_sample);
+  m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

@@ -14,7 +14,8 @@ GaussianHMM: linear-Gaussian state-space model (reference: pyro/distributions/hm
 eliminates time with sequential_gaussian_tensordot (O(log T) rounds of batched Gaussian contractions); here
 log_prob is ONE launch of the Kalman filter / Rauch-Tung-Striebel kernel (pa_gaussian_hmm_fwd_bwd), whose
 smoother pass hands back the gradient with respect to every parameter and the data; rsample_posterior is the same
-filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample).  Whatever the kernels do
+filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample); rsample factors every distinct covariance once
+and runs one lane per sample path (pa_gaussian_hmm_draw).  Whatever the kernels do
 not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
 the plain-torch sequential filter of this file, differentiated by autograd.
 """
@@ -292,6 +293,10 @@ class GaussianHMM(TorchDistribution):
     ``rsample_posterior`` draws the whole latent path given the data: two launches (csrc/gaussian_hmm_sample.hip) for
     the same tensors when nothing needs a gradient, the backward-sampling loop of this module otherwise.
 
+    ``rsample`` draws sample paths of the observations, and with ``prefix_condition(data).rsample(...)`` forecasts:
+    again two launches (csrc/gaussian_hmm_draw.hip) for the same tensors when nothing needs a gradient, after the
+    filter's one launch for a forecast; the generative loop in torch ops, reparameterised, otherwise.
+
     Not built here: ``conjugate_update``, ``GammaGaussianHMM``, ``LinearHMM``, ``IndependentHMM``, ``GaussianMRF``
     and the HMM reparametrisers."""
     arg_constraints = {}
@@ -373,6 +378,14 @@ class GaussianHMM(TorchDistribution):
                 and self.obs_dim <= kernels.GAUSSIAN_HMM_MAX_OBS)
 
     def _kernel_inputs(self, value, batch, T):
+        """The parts as _kernel_parts lays them out, then the data [B, T, obs_dim]."""
+        B = 1
+        for n in batch:
+            B *= int(n)
+        value = value.expand(batch + (T, self.obs_dim)).reshape(B, T, self.obs_dim).contiguous()
+        return self._kernel_parts(batch) + [value]
+
+    def _kernel_parts(self, batch):
         """The parts in the layouts of kernels.gaussian_hmm_fwd_bwd: a parameter whose batch dims are all 1 stays
         shared ([1, ...], batch stride 0), any other is expanded to the B sequences; the time axis keeps its size."""
         B = 1
@@ -386,7 +399,6 @@ class GaussianHMM(TorchDistribution):
                 out.append(p.reshape((1,) + tuple(tail)).contiguous())
             else:
                 out.append(p.expand(batch + tuple(tail)).reshape((B,) + tuple(tail)).contiguous())
-        out.append(value.expand(batch + (T, self.obs_dim)).reshape(B, T, self.obs_dim).contiguous())
         return out
 
     def log_prob(self, value):
@@ -468,21 +480,65 @@ class GaussianHMM(TorchDistribution):
         post = GaussianHMM._from_parts(self._parts[:2] + tuple(left), t, self._validate_args).filter(data)
         return GaussianHMM._from_parts((post.loc, post.covariance_matrix) + tuple(right), f, self._validate_args)
 
-    def rsample(self, sample_shape=torch.Size()):
-        """The generative loop with tensor ops on the parameters' device; needs ``duration``."""
+    def rsample(self, sample_shape=torch.Size(), *, noise=None):
+        """Sample paths of the observations, ``sample_shape + batch_shape + (duration, obs_dim)`` (reference:
+        hmm.py:584-594); needs ``duration``.  With ``L L^T`` the Cholesky factors of the three covariances
+
+            z_0 = m0 + L_0 e_0,   z_t = z_{t-1} F_t + q_t + L_{Q,t} e_t,   x_t = z_t H_t + r_t + L_{R,t} e'_t
+
+        ``noise``: the triple ``(e_0, e, e')`` of standard normals of shapes ``sample_shape + batch_shape`` +
+        ``(hidden_dim,)``, ``(duration, hidden_dim)`` and ``(duration, obs_dim)``; zeros give the mean path.  (The
+        keyword is this package's, as for ``rsample_posterior``.)
+
+        Device tensors in float32 / float64 within the kernels' limits, with nothing requiring a gradient under grad
+        mode, take the two launches of csrc/gaussian_hmm_draw.hip and the result is DETACHED.  Noise that is not given
+        is then ONE ``torch.randn`` of the total size on the parameters' device, split into the three arrays, so
+        ``torch.manual_seed`` reproduces a call -- but the device draws for a given seed differ from those of the
+        torch route (the distribution does not).  A series with a covariance that is not positive definite has NaN
+        paths there.
+
+        Everything else -- grad mode with a parameter or the noise requiring a gradient, CPU tensors, dimensions over
+        16, other dtypes, ``hmm.FUSED_GAUSSIAN_HMM = False`` -- is the generative loop in torch ops: reparameterised
+        in every parameter and in the noise, raising where ``torch.linalg.cholesky`` raises, and without ``noise``
+        drawing per step exactly as it always has."""
         if self.duration is None:
             raise ValueError("GaussianHMM.rsample needs a duration (time-homogeneous parameters do not tell it)")
         m0, P0, F, q, Q, H, r, R = self._parts
+        T, h, o = self.duration, self.hidden_dim, self.obs_dim
         shape = torch.Size(sample_shape) + self.batch_shape
+        shapes = (shape + (h,), shape + (T, h), shape + (T, o))
+        if noise is not None:
+            noise = tuple(noise)
+            if len(noise) != 3 or any(e.shape != s for e, s in zip(noise, shapes)):
+                raise ValueError("expected noise as a triple of shapes {}, {} and {}, got {}".format(
+                    *(tuple(s) for s in shapes), [tuple(e.shape) for e in noise]))
+        tensors = self._parts + (noise or ())
+        needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+        from .. import kernels
+        if (not needs_grad and FUSED_GAUSSIAN_HMM and m0.dtype in (torch.float32, torch.float64)
+                and all(kernels.on_device(t) and t.dtype == m0.dtype for t in tensors)
+                and h <= kernels.GAUSSIAN_HMM_MAX_HIDDEN and o <= kernels.GAUSSIAN_HMM_MAX_OBS):
+            if noise is None:
+                sizes = [s.numel() for s in shapes]
+                flat = torch.randn(sum(sizes), dtype=m0.dtype, device=m0.device)
+                noise = [e.reshape(s) for e, s in zip(flat.split(sizes), shapes)]
+            args = [t.detach() for t in self._kernel_parts(self.batch_shape)]
+            B = self.batch_shape.numel()
+            eps = [e.detach().reshape((-1, B) + tuple(s[len(shape):])).contiguous() for e, s in zip(noise, shapes)]
+            x, _ = kernels.gaussian_hmm_draw(*args, T, *eps)
+            return x.reshape(shapes[2])
 
-        def draw(loc, cov):
+        def draw(loc, cov, given):
             L = torch.linalg.cholesky(cov)
-            eps = torch.randn(shape + loc.shape[-1:], dtype=loc.dtype, device=loc.device)
+            eps = torch.randn(shape + loc.shape[-1:], dtype=loc.dtype, device=loc.device) if given is None else given
             return loc + (L @ eps.unsqueeze(-1)).squeeze(-1)
 
-        z = draw(m0, P0)
+        e0, ez, ex = noise or (None, None, None)
+        z = draw(m0, P0, e0)
         xs = []
-        for t in range(self.duration):
-            z = (z.unsqueeze(-2) @ _step(F, t, 2)).squeeze(-2) + draw(_step(q, t, 1), _step(Q, t, 2))
-            xs.append((z.unsqueeze(-2) @ _step(H, t, 2)).squeeze(-2) + draw(_step(r, t, 1), _step(R, t, 2)))
+        for t in range(T):
+            z = (z.unsqueeze(-2) @ _step(F, t, 2)).squeeze(-2) \
+                + draw(_step(q, t, 1), _step(Q, t, 2), None if ez is None else ez[..., t, :])
+            xs.append((z.unsqueeze(-2) @ _step(H, t, 2)).squeeze(-2)
+                      + draw(_step(r, t, 1), _step(R, t, 2), None if ex is None else ex[..., t, :]))
         return torch.stack(xs, dim=-2)

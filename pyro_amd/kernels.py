@@ -816,12 +816,11 @@ GAUSSIAN_HMM_MAX_HIDDEN = 16
 GAUSSIAN_HMM_MAX_OBS = 16
 
 
-def _gaussian_hmm_layout(params, x):
-    """The checks the two state-space wrappers share -> (B, T, hidden, obs, the fourteen element strides in the order
-    of the C arguments, the step-axis sizes of the six timed parameters)."""
-    _require_gpu(x, *params)
-    assert x.dim() == 3 and x.is_contiguous()
-    B, T, o = x.shape
+def _gaussian_hmm_param_layout(params, B, T, o, dtype):
+    """The checks of the eight parameters of a state-space model of B sequences, T steps and ``o`` observed dims in
+    ``dtype`` -> (hidden, the fourteen element strides in the order of the C arguments, the step-axis sizes of the
+    six timed parameters)."""
+    _require_gpu(*params)
     h = params[0].shape[-1]
     assert T >= 1 and h >= 1 and o >= 1
     if h > GAUSSIAN_HMM_MAX_HIDDEN or o > GAUSSIAN_HMM_MAX_OBS:
@@ -831,7 +830,7 @@ def _gaussian_hmm_layout(params, x):
     strides, steps = [], []
     for i, (p, ev) in enumerate(zip(params, events)):
         timed = i >= 2
-        assert p.dtype == x.dtype and p.is_contiguous(), "gaussian_hmm: contiguous parameters of x's dtype"
+        assert p.dtype == dtype and p.is_contiguous(), "gaussian_hmm: contiguous parameters of x's dtype"
         assert p.dim() == len(ev) + (2 if timed else 1) and tuple(p.shape[-len(ev):]) == ev, \
             "gaussian_hmm: parameter %d has shape %s" % (i, tuple(p.shape))
         assert p.shape[0] in (1, B) and (not timed or p.shape[1] in (1, T))
@@ -843,17 +842,28 @@ def _gaussian_hmm_layout(params, x):
         if timed:
             strides.append(0 if Tp == 1 else n)
             steps.append(Tp)
+    return h, strides, steps
+
+
+def _gaussian_hmm_layout(params, x):
+    """The checks the state-space wrappers with data share -> (B, T, hidden, obs, the fourteen element strides in the
+    order of the C arguments, the step-axis sizes of the six timed parameters)."""
+    _require_gpu(x, *params)
+    assert x.dim() == 3 and x.is_contiguous()
+    B, T, o = x.shape
+    h, strides, steps = _gaussian_hmm_param_layout(params, B, T, o, x.dtype)
     return B, T, h, o, strides, steps
 
 
 def _gaussian_hmm_args(params, x, strides, B, T, h, o):
-    """The leading C arguments of both entry points: dtype, the parameters with their strides, x and the sizes."""
-    args = [_dtype(x), _ptr(params[0]), strides[0], _ptr(params[1]), strides[1]]
+    """The leading C arguments of the entry points: dtype, the parameters with their strides, x (None: the entry
+    point takes no data) and the sizes."""
+    args = [_dtype(params[0]), _ptr(params[0]), strides[0], _ptr(params[1]), strides[1]]
     k = 2
     for p in params[2:]:
         args += [_ptr(p), strides[k], strides[k + 1]]
         k += 2
-    return args + [_ptr(x), B, T, h, o]
+    return args + ([] if x is None else [_ptr(x)]) + [B, T, h, o]
 
 
 def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filter=False):
@@ -918,6 +928,40 @@ def gaussian_hmm_sample(m0, P0, F, q, Q, H, r, R, x, eps, need_maps=False):
     args += [_ptr(ws), nbytes, _stream()]
     check(lib.pa_gaussian_hmm_sample(*args))
     return z, maps
+
+
+def gaussian_hmm_draw(m0, P0, F, q, Q, H, r, R, T, eps0, eps_z, eps_x, need_states=False):
+    """Forward draws of that model in two launches (pa_gaussian_hmm_draw): z_0 = m0 + L_0 e_0,
+    z_t = z_{t-1} F_t + q_t + L_{Q,t} e_t, x_t = z_t H_t + r_t + L_{R,t} e'_t for t = 1..T, with L L^T the Cholesky
+    factors of P0, Q_t, R_t.  Parameters in the layouts of gaussian_hmm_fwd_bwd (there is no data, hence ``T``);
+    the standard normal noise ``eps0`` [S, B, h], ``eps_z`` [S, B, T, h], ``eps_x`` [S, B, T, o] contiguous (zeros
+    give the mean path).  -> (x [S, B, T, o], z [S, B, T, h] with ``need_states``, else None).  Launch 1 factors
+    every DISTINCT covariance once -- a shared, time-homogeneous one a single time -- launch 2 runs one lane per
+    draw.  A sequence with a non-positive pivot in a factor it uses gets NaN throughout.  Nothing here is
+    differentiable.  hidden or obs over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    _require_gpu(eps0, eps_z, eps_x)
+    assert eps0.dim() == 3 and H.dim() == 4, "gaussian_hmm_draw: eps0 [S, B, hidden], H [B | 1, T | 1, hidden, obs]"
+    S, B = eps0.shape[:2]
+    o, T = H.shape[-1], int(T)
+    h, strides, _ = _gaussian_hmm_param_layout(params, B, T, o, eps0.dtype)
+    for e, shape in ((eps0, (S, B, h)), (eps_z, (S, B, T, h)), (eps_x, (S, B, T, o))):
+        assert tuple(e.shape) == shape and e.dtype == eps0.dtype and e.is_contiguous(), \
+            "gaussian_hmm_draw: eps0 [S, B, hidden], eps_z [S, B, T, hidden], eps_x [S, B, T, obs] contiguous of " \
+            "the parameters' dtype"
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, dtype=eps0.dtype, device=eps0.device)     # noqa: E731
+    x = new(S, B, T, o)
+    z = new(S, B, T, h) if need_states else None
+    # (only the factors the strides make distinct: see include/pyro_amd.h)
+    Bw = B if any(p.shape[0] != 1 for p in (P0, Q, R)) else 1
+    Tw = T if any(p.shape[1] != 1 for p in (Q, R)) else 1
+    nbytes = lib.pa_gaussian_hmm_draw_workspace(_dtype(eps0), Bw, Tw, h, o)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=eps0.device) if nbytes else None
+    args = _gaussian_hmm_args(params, None, strides, B, T, h, o) + [S, _ptr(eps0), _ptr(eps_z), _ptr(eps_x)]
+    args += [_ptr(x), _ptr(z), _ptr(ws), nbytes, _stream()]
+    check(lib.pa_gaussian_hmm_draw(*args))
+    return x, z
 
 
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):

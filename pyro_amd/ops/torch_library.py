@@ -143,6 +143,12 @@ def _register():
         maps = [x.new_empty((B, T, h)), x.new_empty((B, T, h, h)), x.new_empty((B, T, h, h))] if need_maps else []
         return x.new_empty((eps.shape[0], B, T, h)), maps
 
+    @lib.register_fake("pyro_amd::gaussian_hmm_draw")
+    def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, T, eps0, eps_z, eps_x, need_states):
+        S, B, h = eps0.shape
+        states = [eps0.new_empty((S, B, T, h))] if need_states else []
+        return eps0.new_empty((S, B, T, obs.shape[-1])), states
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -624,4 +630,4 @@ def registered_ops():
 # the typed C++ ops of csrc/torch_ops.cpp beside the GLM site's (round 6): real argument lists, loadable from C++
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
-             "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample")
+             "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw")
