@@ -905,14 +905,15 @@ int pa_logchain_decode(int dtype, const void* unary, const void* pairwise, int64
  *   grad_* (all nine or none): d log_prob[b] / d input, contiguous [B, ...] for m0 and P0, [B, T, obs] for x,
  *     [B, T, ...] for a parameter with a step stride and [B, ...] (summed over the steps inside the kernel, in the
  *     fixed order of the backward sweep) for one without; the sum over sequences of a batch-shared parameter is
- *     the caller's.  Covariance gradients are the symmetric dL/dSigma.  With zbar, Ps the smoothed moments,
- *     C_t = Cov(z_{t-1}, z_t | x), ebar_t = zbar_t - zbar_{t-1} F_t - q_t, ubar_t = x_t - zbar_t H_t - r_t:
- *       d/dm0 = P0^-1 (zbar_0 - m0)           d/dP0 = P0^-1 (Ps_0 + (zbar_0 - m0)(zbar_0 - m0)^T - P0) P0^-1 / 2
- *       d/dq  = Q^-1 ebar                      d/dQ  = Q^-1 (E - Q) Q^-1 / 2,
- *                                               E = Ps_t - F^T C - C^T F + F^T Ps_{t-1} F + ebar ebar^T
- *       d/dF  = (C - Ps_{t-1} F + zbar_{t-1} ebar^T) Q^-1
- *       d/dr  = R^-1 ubar = -d/dx              d/dR  = R^-1 (H^T Ps_t H + ubar ubar^T - R) R^-1 / 2
- *       d/dH  = (-Ps_t H + zbar_t ubar^T) R^-1
+ *     the caller's.  Covariance gradients are the symmetric dL/dSigma.  They are the adjoint of the filter's own
+ *     steps: with y, S, K = P^p H S^-1 and w = S^-1 y of step t recomputed from the filtered (m_{t-1}, P_{t-1}), and
+ *     (mu, M) = d l_{>t} / d (m_t, P_t) carried down from zero at t = T,
+ *       d/dr  = rho = w - K^T mu = -d/dx      d/dR  = Sigma = (rho rho^T - S^-1) / 2 + K^T (M - mu mu^T / 2) K
+ *       d/dH  = m^p rho^T + (P^p mu) w^T + 2 P^p H Sigma - 2 P^p M K
+ *       d/dq  = lambda = H rho + mu           d/dQ  = Lambda = H Sigma H^T + sym(mu (H w)^T) + M - M K H^T - H K^T M
+ *       d/dF  = m_{t-1} lambda^T + 2 P_{t-1} F Lambda;     mu <- F lambda,  M <- F Lambda F^T
+ *       d/dm0 = mu_0                          d/dP0 = M_0
+ *     (no inverse of Q, R or P0 enters, so float32 keeps its digits when R is small or P0 large).
  * A sequence whose innovation covariance has a non-positive pivot gets NaN for log_prob, the filter outputs and
  * every gradient (the gradients also on such a pivot of P^p, Q, R or P0); other sequences are untouched.  No
  * atomics: bit-reproducible.  hidden or obs > 16: PA_ERR_UNSUPPORTED.  B = 0: PA_OK without a launch.

@@ -5,10 +5,11 @@
 // contractions, and autograd differentiates through every one of them -- hundreds of small launches per gradient
 // for a few hundred steps.  Here (row vectors, as the reference writes the model)
 //     z_0 ~ N(m0, P0),   z_t = z_{t-1} F_t + N(q_t, Q_t),   x_t = z_t H_t + N(r_t, R_t),   t = 1..T
-// one wave per sequence runs the Kalman filter forward and, when gradients are asked for, the Rauch-Tung-Striebel
-// sweep backward in the same launch.  The expected complete-data score under the smoothed posterior IS the gradient
-// of the log-likelihood (Fisher's identity) -- the relation logchain.hip uses for the discrete chain: the posteriors
-// are the gradient.
+// one wave per sequence runs the Kalman filter forward and, when gradients are asked for, the adjoint of that filter
+// backward in the same launch: the derivative of the filter's own arithmetic, step by step.  (Until the edge tests the
+// sweep was the Rauch-Tung-Striebel smoother with the expected complete-data score as the gradient -- Fisher's
+// identity: exact, but differences sandwiched between Q^-1, R^-1 and P0^-1, which cost float32 up to all of its digits
+// when R is small or P0 large and a factor of ten where the hidden dimension exceeds the observed one.)
 //
 // Forward: the filter of gaussian_hmm.h (GhFilter: the recurrence, where P^p is symmetrised, the bad-pivot rule), shared
 // with gaussian_hmm_sample.hip; per step this kernel adds  log_prob += -|v|^2 / 2 - sum log diag L - obs / 2 log 2 pi.
@@ -17,10 +18,16 @@
 // (gradients only: log_prob is what the forward pass alone gives).
 //
 // Backward, per step t = T..1, from the filtered (m_{t-1}, P_{t-1}) kept in the workspace (hidden + hidden^2
-// elements per step; the predicted moments are recomputed): smoother gain G = P_{t-1} F (P^p)^-1,
-//     zbar_{t-1} = m_{t-1} + G (zbar_t - m^p),  Ps_{t-1} = sym(P_{t-1} + G (Ps_t - P^p) G^T),  C = G Ps_t,
-// and the gradient rows of include/pyro_amd.h.  A parameter with step stride 0 has its gradient summed over the
-// steps in registers, in the order of the sweep (t = T down to 1) -- a fixed order, no atomics: bit-reproducible.
+// elements per step; the predicted moments, S, the gain K = P^p H S^-1 and w = S^-1 y are recomputed), with
+// (mu, M) = d l_{>t} / d (m_t, P_t) carried down (zero at t = T; at the end the gradients of m0 and P0):
+//     rho = w - K^T mu = d/dr = -d/dx,   Sigma = (rho rho^T - S^-1) / 2 + K^T (M - mu mu^T / 2) K = d/dR,
+//     d/dH = m^p rho^T + (P^p mu) w^T + 2 P^p H Sigma - 2 P^p M K,
+//     lambda = H rho + mu = d/dq,   Lambda = H Sigma H^T + sym(mu (H w)^T) + M - M K H^T - H K^T M = d/dQ,
+//     d/dF = m_{t-1} lambda^T + 2 P_{t-1} F Lambda,   mu <- F lambda,   M <- F Lambda F^T.
+// No inverse but S^-1 enters; the sums accumulate in double also for float32.  The pivots of P^p, Q, R and P0 are
+// still checked (a Cholesky sweep over a copy) for the NaN convention above.  A parameter with step stride 0 has its
+// gradient summed over the steps in registers, in the order of the sweep (t = T down to 1) -- a fixed order, no
+// atomics: bit-reproducible.
 //
 // Mapping: the block is ONE wave; every matrix lives in LDS with row stride MD + 1 (MD = 8 or 16: the padded
 // dimension; the odd stride keeps both the row- and the column-indexed accesses of the 64 lanes off each other's
@@ -30,10 +37,10 @@
 //
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage), one wave of 64 lanes per block:
 //     instantiation    VGPRs      SGPRs  scratch   LDS bytes   waves / SIMD
-//     <float , 8>      132        106    0         5832        3
-//     <float , 16>     256 + 12   106    0         21384       1
-//     <double, 8>      172        106    0         11664       2
-//     <double, 16>     256 + 65   106    0         42768       1
+//     <float , 8>      135        106    0         5832        3
+//     <float , 16>     256 + 5    106    0         21384       1
+//     <double, 8>      168        106    0         11664       2
+//     <double, 16>     256 + 60   106    0         42768       1
 // (+ n: accumulation registers the 16-wide instantiations use as spill space; nothing goes to scratch memory)
 #include <limits>
 
@@ -142,30 +149,40 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
     fill_nan();
     return;
   }
-  // dst = src^-1 for a symmetric positive definite n x n matrix whose elements ``own`` lists (sL is the scratch)
-  auto spd_inverse = [&](const T* src, T* dst, int n, const int (&own)[EPL]) {
+  // a pivot check alone: the Cholesky sweep over a copy of the n x n matrix ``src`` in sL; ends with a barrier
+  auto check_pivots = [&](const T* src, int n, const int (&own)[EPL]) {
 #pragma unroll
     for (int k = 0; k < EPL; ++k)
-      if (own[k] >= 0) {
-        sL[own[k]] = src[own[k]];
-        dst[own[k]] = own[k] / LD == own[k] % LD ? T(1) : T(0);
-      }
+      if (own[k] >= 0) sL[own[k]] = src[own[k]];
     __syncthreads();
     gh_cholesky<T, MD>(sL, n, lane, bad);
-    if (lane < n) {
-      gh_forward_sub<T, LD>(sL, dst + lane, LD, n);
-      gh_backward_sub<T, LD>(sL, dst + lane, LD, n);
-    }
     __syncthreads();
   };
 
-  if (lane < h) vzs[lane] = vm[lane];
+  using AT = double;             // the sweep's sums accumulate in double, also for float32
+  T* const sMa = sPs;            // M = d l_{>t} / d P_t, carried down the sweep
+  T* const sLa = sPm;            // Lambda = d l / d P^p_t
+  T* const sFL = sM;             // F Lambda
+  T* const sPH = sE;             // P^p H
+  T* const sK = sB;              // the gain K = P^p H S^-1
+  T* const sMK = sQi;            // M K
+  T* const sSi = sRi;            // S^-1
+  T* const sSg = sV;             // Sigma = d l / d S_t
+  T* const sHS = sX;             // H Sigma
+  T* const vw = f.vy;            // S^-1 y
+  T* const vmu = vzs;            // mu = d l_{>t} / d m_t, carried down the sweep
+  T* const vla = vzp;            // lambda = d l / d m^p_t
+  T* const vpm = vd;             // P^p mu
+  T* const vhw = ve;             // H w
+  T* const vrho = vu;            // rho = w - K^T mu
+
+  if (lane < h) vmu[lane] = T(0);
 #pragma unroll
   for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) sPs[lhh[k]] = sP[lhh[k]];
+    if (lhh[k] >= 0) sMa[lhh[k]] = T(0);
   __syncthreads();
-  if (!a.m.Q_ss) spd_inverse(sQ, sQi, h, lhh);
-  if (!a.m.R_ss) spd_inverse(sR, sRi, o, loo);
+  if (!a.m.Q_ss) check_pivots(sQ, h, lhh);
+  if (!a.m.R_ss) check_pivots(sR, o, loo);
 
   T aF[EPL], aQ[EPL], aH[EPL], aR[EPL], aq = T(0), ar = T(0);
 #pragma unroll
@@ -200,162 +217,165 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
       load_filtered(t - 1);
     }
     __syncthreads();
-    if (a.m.Q_ss) spd_inverse(sQ, sQi, h, lhh);
-    if (a.m.R_ss) spd_inverse(sR, sRi, o, loo);
-    f.predict(sL);                                                 // vmp, sPp (= sL), sA = F^T P_{t-1}
-    gh_cholesky<T, MD>(sL, h, lane, bad);
-    if (lane < h) {                                              // column i of sA <- (P^p)^-1 column: sA[j, i] = G[i, j]
-      gh_forward_sub<T, LD>(sL, sA + lane, LD, h);
-      gh_backward_sub<T, LD>(sL, sA + lane, LD, h);
-      vd[lane] = vzs[lane] - vmp[lane];
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sB[lhh[k]] = sPs[lhh[k]] - sPp[lhh[k]];
+    if (a.m.Q_ss) check_pivots(sQ, h, lhh);
+    if (a.m.R_ss) check_pivots(sR, o, loo);
+    f.predict(sL);                                                 // vmp, sPp (and a copy in sL), sA = F^T P_{t-1}
+    gh_cholesky<T, MD>(sL, h, lane, bad);                          // (the pivots of P^p)
     __syncthreads();
-    if (lane < h) {                                              // zbar_{t-1}
-      T s = vm[lane];
-      for (int j = 0; j < h; ++j) s += sA[j * LD + lane] * vd[j];
-      vzp[lane] = s;
-    }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {                                         // sC = G (Ps_t - P^p), sX = C_t = G Ps_t
-        const int i = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0), s2 = T(0);
-        for (int j = 0; j < h; ++j) {
-          const T g = sA[j * LD + i];
-          s += g * sB[j * LD + c];
-          s2 += g * sPs[j * LD + c];
-        }
-        sC[lhh[k]] = s;
-        sX[lhh[k]] = s2;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {                                         // sB = P_{t-1} + G (Ps_t - P^p) G^T
-        const int i = lhh[k] / LD, c = lhh[k] % LD;
-        T s = sP[lhh[k]];
-        for (int j = 0; j < h; ++j) s += sC[i * LD + j] * sA[j * LD + c];
-        sB[lhh[k]] = s;
-      }
-    if (lane < h) {                                              // ebar
-      T s = vzs[lane] - vq[lane];
-      for (int i = 0; i < h; ++i) s -= vzp[i] * sF[i * LD + lane];
-      ve[lane] = s;
-    }
-    if (lane < o) {                                              // ubar
+    // the step's update once more: y, P^p H, S = L L^T, K, w = S^-1 y, S^-1
+    if (lane < o) {
       T s = vx[lane] - vr[lane];
-      for (int j = 0; j < h; ++j) s -= vzs[j] * sH[j * LD + lane];
-      vu[lane] = s;
+      for (int j = 0; j < h; ++j) s -= vmp[j] * sH[j * LD + lane];
+      vw[lane] = s;
+    }
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      if (lho[k] >= 0) {
+        const int j = lho[k] / LD, c = lho[k] % LD;
+        T s = T(0);
+        for (int i = 0; i < h; ++i) s += sPp[j * LD + i] * sH[i * LD + c];
+        sPH[lho[k]] = s;
+        sK[lho[k]] = s;
+      }
+      if (loo[k] >= 0) sSi[loo[k]] = loo[k] / LD == loo[k] % LD ? T(1) : T(0);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) {                                         // Ps_{t-1}, symmetrised
-        const int i = lhh[k] / LD, c = lhh[k] % LD;
-        sPm[lhh[k]] = T(0.5) * (sB[i * LD + c] + sB[c * LD + i]);
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      if (lhh[k] >= 0) {                                         // sM = Ps_{t-1} F
-        const int i = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0);
-        for (int j = 0; j < h; ++j) s += sPm[i * LD + j] * sF[j * LD + c];
-        sM[lhh[k]] = s;
-      }
-      if (lho[k] >= 0) {                                         // sN = Ps_t H
-        const int j = lho[k] / LD, c = lho[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sPs[j * LD + i] * sH[i * LD + c];
-        sN[lho[k]] = s;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        // sC = C - Ps_{t-1} F + zbar_{t-1} ebar^T                       ([old, new])
-        sC[lhh[k]] = sX[lhh[k]] - sM[lhh[k]] + vzp[j] * ve[c];
-        // sE = Ps_t - F^T C - C^T F + F^T Ps_{t-1} F + ebar ebar^T - Q
-        T s = sPs[lhh[k]] + ve[j] * ve[c] - sQ[lhh[k]];
-        for (int i = 0; i < h; ++i)
-          s += sF[i * LD + j] * (sM[i * LD + c] - sX[i * LD + c]) - sX[i * LD + j] * sF[i * LD + c];
-        sE[lhh[k]] = s;
-      }
-      if (lho[k] >= 0) {                                         // sB = -Ps_t H + zbar_t ubar^T
-        const int j = lho[k] / LD, c = lho[k] % LD;
-        sB[lho[k]] = vzs[j] * vu[c] - sN[lho[k]];
-      }
-      if (loo[k] >= 0) {                                         // sV = H^T Ps_t H + ubar ubar^T - R
+      if (loo[k] >= 0) {
         const int r_ = loo[k] / LD, c = loo[k] % LD;
-        T s = vu[r_] * vu[c] - sR[loo[k]];
-        for (int j = 0; j < h; ++j) s += sH[j * LD + r_] * sN[j * LD + c];
-        sV[loo[k]] = s;
+        T s = sR[loo[k]];
+        for (int j = 0; j < h; ++j) s += sH[j * LD + r_] * sPH[j * LD + c];
+        sL[loo[k]] = s;
       }
+    __syncthreads();
+    gh_cholesky<T, MD>(sL, o, lane, bad);
+    if (lane < h) {                                              // row j of K
+      gh_forward_sub<T, LD>(sL, sK + lane * LD, 1, o);
+      gh_backward_sub<T, LD>(sL, sK + lane * LD, 1, o);
+    } else if (lane == h) {
+      gh_forward_sub<T, LD>(sL, vw, 1, o);
+      gh_backward_sub<T, LD>(sL, vw, 1, o);
+    } else if (lane <= h + o) {
+      gh_forward_sub<T, LD>(sL, sSi + (lane - h - 1), LD, o);
+      gh_backward_sub<T, LD>(sL, sSi + (lane - h - 1), LD, o);
     }
     __syncthreads();
-    if (lane < h) {                                              // d/dq = Q^-1 ebar
-      T s = T(0);
-      for (int c = 0; c < h; ++c) s += sQi[lane * LD + c] * ve[c];
-      if (a.m.q_ss) gq[(int64_t)t * h + lane] = s; else aq += s;
+    if (lane < o) {                                              // rho = w - K^T mu
+      AT s = vw[lane];
+      for (int j = 0; j < h; ++j) s -= (AT)sK[j * LD + lane] * vmu[j];
+      vrho[lane] = s;
     }
-    if (lane < o) {                                              // d/dr = R^-1 ubar = -d/dx
-      T s = T(0);
-      for (int c = 0; c < o; ++c) s += sRi[lane * LD + c] * vu[c];
+    if (lane < h) {                                              // H w, P^p mu
+      AT s = AT(0), s2 = AT(0);
+      for (int c = 0; c < o; ++c) s += (AT)sH[lane * LD + c] * vw[c];
+      for (int i = 0; i < h; ++i) s2 += (AT)sPp[lane * LD + i] * vmu[i];
+      vhw[lane] = s;
+      vpm[lane] = s2;
+    }
+#pragma unroll
+    for (int k = 0; k < EPL; ++k)
+      if (lho[k] >= 0) {                                         // M K
+        const int j = lho[k] / LD, c = lho[k] % LD;
+        AT s = AT(0);
+        for (int i = 0; i < h; ++i) s += (AT)sMa[j * LD + i] * sK[i * LD + c];
+        sMK[lho[k]] = s;
+      }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < EPL; ++k)
+      if (loo[k] >= 0) {                 // Sigma = (rho rho^T - S^-1) / 2 + K^T (M - mu mu^T / 2) K
+        const int r_ = loo[k] / LD, c = loo[k] % LD;
+        const AT kr = (AT)vw[r_] - vrho[r_], kc = (AT)vw[c] - vrho[c];
+        AT s = AT(0.5) * ((AT)vrho[r_] * vrho[c] - sSi[loo[k]] - kr * kc);
+        for (int j = 0; j < h; ++j) s += (AT)sK[j * LD + r_] * sMK[j * LD + c];
+        sSg[loo[k]] = s;
+      }
+    if (lane < h) {                                              // lambda = H rho + mu
+      AT s = vmu[lane];
+      for (int c = 0; c < o; ++c) s += (AT)sH[lane * LD + c] * vrho[c];
+      vla[lane] = s;
+    }
+    __syncthreads();
+    if (lane < o) {                                              // d/dr = rho = -d/dx
+      const T s = vrho[lane];
       if (a.m.r_ss) gr[(int64_t)t * o + lane] = s; else ar += s;
       gx[(int64_t)t * o + lane] = -s;
     }
+    if (lane < h) {                                              // d/dq = lambda
+      const T s = vla[lane];
+      if (a.m.q_ss) gq[(int64_t)t * h + lane] = s; else aq += s;
+    }
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
       const int e = lane + 64 * k;
-      if (lhh[k] >= 0) {
-        const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0), s2 = T(0);
-        for (int i = 0; i < h; ++i) {
-          s += sC[j * LD + i] * sQi[i * LD + c];                 // d/dF = (...) Q^-1
-          s2 += sQi[j * LD + i] * sE[i * LD + c];                // sM = Q^-1 E
-        }
-        if (a.m.F_ss) gF[(int64_t)t * hh + e] = s; else aF[k] += s;
-        sM[lhh[k]] = s2;
+      if (loo[k] >= 0) {                                         // d/dR = Sigma
+        const T s = sSg[loo[k]];
+        if (a.m.R_ss) gR[(int64_t)t * oo + e] = s; else aR[k] += s;
       }
-      if (lho[k] >= 0) {                                         // d/dH = (...) R^-1
+      if (lho[k] >= 0) {
         const int j = lho[k] / LD, c = lho[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < o; ++i) s += sB[j * LD + i] * sRi[i * LD + c];
+        // d/dH = m^p rho^T + (P^p mu) w^T + 2 P^p H Sigma - 2 P^p M K;  sHS = H Sigma
+        AT s = (AT)vmp[j] * vrho[c] + (AT)vpm[j] * vw[c], s2 = AT(0), s3 = AT(0);
+        for (int i = 0; i < o; ++i) {
+          s2 += (AT)sPH[j * LD + i] * sSg[i * LD + c];
+          s3 += (AT)sH[j * LD + i] * sSg[i * LD + c];
+        }
+        for (int i = 0; i < h; ++i) s2 -= (AT)sPp[j * LD + i] * sMK[i * LD + c];
+        s += AT(2) * s2;
         if (a.m.H_ss) gH[(int64_t)t * ho + e] = s; else aH[k] += s;
-      }
-      if (loo[k] >= 0) {                                         // sPp = R^-1 V
-        const int r_ = loo[k] / LD, c = loo[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < o; ++i) s += sRi[r_ * LD + i] * sV[i * LD + c];
-        sPp[loo[k]] = s;
+        sHS[lho[k]] = s3;
       }
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
       const int e = lane + 64 * k;
-      if (lhh[k] >= 0) {                                         // d/dQ = Q^-1 E Q^-1 / 2
+      if (lhh[k] >= 0) {
+        // Lambda = H Sigma H^T + (mu (H w)^T + (H w) mu^T) / 2 + M - M K H^T - H K^T M = d/dQ
         const int j = lhh[k] / LD, c = lhh[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < h; ++i) s += sM[j * LD + i] * sQi[i * LD + c];
-        s *= T(0.5);
+        AT s = sMa[lhh[k]] + AT(0.5) * ((AT)vmu[j] * vhw[c] + (AT)vhw[j] * vmu[c]);
+        for (int i = 0; i < o; ++i)
+          s += ((AT)sHS[j * LD + i] - sMK[j * LD + i]) * sH[c * LD + i] - (AT)sMK[c * LD + i] * sH[j * LD + i];
+        sLa[lhh[k]] = s;
         if (a.m.Q_ss) gQ[(int64_t)t * hh + e] = s; else aQ[k] += s;
-        sPs[lhh[k]] = sPm[lhh[k]];                               // (Ps_t was last read before the barrier above)
-      }
-      if (loo[k] >= 0) {                                         // d/dR = R^-1 V R^-1 / 2
-        const int r_ = loo[k] / LD, c = loo[k] % LD;
-        T s = T(0);
-        for (int i = 0; i < o; ++i) s += sPp[r_ * LD + i] * sRi[i * LD + c];
-        s *= T(0.5);
-        if (a.m.R_ss) gR[(int64_t)t * oo + e] = s; else aR[k] += s;
       }
     }
-    if (lane < h) vzs[lane] = vzp[lane];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < EPL; ++k)
+      if (lhh[k] >= 0) {                                         // F Lambda
+        const int j = lhh[k] / LD, c = lhh[k] % LD;
+        AT s = AT(0);
+        for (int i = 0; i < h; ++i) s += (AT)sF[j * LD + i] * sLa[i * LD + c];
+        sFL[lhh[k]] = s;
+      }
+    __syncthreads();
+    T nM[EPL];
+    AT nmu = AT(0);
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      const int e = lane + 64 * k;
+      nM[k] = T(0);
+      if (lhh[k] >= 0) {                 // d/dF = m_{t-1} lambda^T + 2 P_{t-1} F Lambda;  M_{t-1} = F Lambda F^T
+        const int j = lhh[k] / LD, c = lhh[k] % LD;
+        AT s = AT(0), s2 = AT(0);
+        for (int i = 0; i < h; ++i) {
+          s += (AT)sP[j * LD + i] * sFL[i * LD + c];
+          s2 += (AT)sFL[j * LD + i] * sF[c * LD + i];
+        }
+        s = (AT)vm[j] * vla[c] + AT(2) * s;
+        if (a.m.F_ss) gF[(int64_t)t * hh + e] = s; else aF[k] += s;
+        nM[k] = s2;
+      }
+    }
+    if (lane < h)                                                // mu_{t-1} = F lambda
+      for (int c = 0; c < h; ++c) nmu += (AT)sF[lane * LD + c] * vla[c];
+    __syncthreads();
+    if (lane < h) vmu[lane] = nmu;
+#pragma unroll
+    for (int k = 0; k < EPL; ++k)
+      if (lhh[k] >= 0) sMa[lhh[k]] = nM[k];
   }
   __syncthreads();
   // the step-summed gradients of the time-homogeneous parameters
@@ -371,39 +391,12 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
     if (lho[k] >= 0 && !a.m.H_ss) gH[e] = aH[k];
     if (loo[k] >= 0 && !a.m.R_ss) gR[e] = aR[k];
   }
-  // the initial state: (vm, sP) hold (m0, P0) since step 1 of the sweep, (vzs, sPs) = (zbar_0, Ps_0)
-  spd_inverse(sP, sQi, h, lhh);
-  if (lane < h) vd[lane] = vzs[lane] - vm[lane];
-  __syncthreads();
+  // the initial state: (mu_0, M_0) are its gradients; sP holds P0 since step 1 of the sweep
+  if (lane < h) gm0[lane] = vmu[lane];
 #pragma unroll
   for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) {
-      const int j = lhh[k] / LD, c = lhh[k] % LD;
-      sB[lhh[k]] = sPs[lhh[k]] + vd[j] * vd[c] - sP[lhh[k]];
-    }
-  if (lane < h) {
-    T s = T(0);
-    for (int c = 0; c < h; ++c) s += sQi[lane * LD + c] * vd[c];
-    gm0[lane] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) {
-      const int j = lhh[k] / LD, c = lhh[k] % LD;
-      T s = T(0);
-      for (int i = 0; i < h; ++i) s += sQi[j * LD + i] * sB[i * LD + c];
-      sA[lhh[k]] = s;
-    }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) {
-      const int j = lhh[k] / LD, c = lhh[k] % LD;
-      T s = T(0);
-      for (int i = 0; i < h; ++i) s += sA[j * LD + i] * sQi[i * LD + c];
-      gP0[lane + 64 * k] = T(0.5) * s;
-    }
+    if (lhh[k] >= 0) gP0[lane + 64 * k] = sMa[lhh[k]];
+  check_pivots(sP, h, lhh);
   if (bad) fill_nan();
 }
 

@@ -12,9 +12,9 @@ returns the log-likelihood of every batch element and, as its gradient, the post
 
 GaussianHMM: linear-Gaussian state-space model (reference: pyro/distributions/hmm.py:434-741).  The reference
 eliminates time with sequential_gaussian_tensordot (O(log T) rounds of batched Gaussian contractions); here
-log_prob is ONE launch of the Kalman filter / Rauch-Tung-Striebel kernel (pa_gaussian_hmm_fwd_bwd), whose
-smoother pass hands back the gradient with respect to every parameter and the data; rsample_posterior is the same
-filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample); rsample factors every distinct covariance once
+log_prob is ONE launch of the Kalman filter kernel (pa_gaussian_hmm_fwd_bwd), whose backward pass -- the adjoint
+of the filter's own steps -- hands back the gradient with respect to every parameter and the data;
+rsample_posterior is the same filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample); rsample factors every distinct covariance once
 and runs one lane per sample path (pa_gaussian_hmm_draw).  Whatever the kernels do
 not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
 the plain-torch sequential filter of this file, differentiated by autograd.

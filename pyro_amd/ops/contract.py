@@ -504,8 +504,8 @@ class _LogChain(torch.autograd.Function):
 
 @_dispatcher_op("gaussian_hmm")
 class _GaussianHMM(torch.autograd.Function):
-    """log p(x) of a linear-Gaussian state-space model for every sequence (Kalman filter) with the smoother's
-    expected complete-data score as gradient, ONE launch (pa_gaussian_hmm_fwd_bwd).  Arguments in the layouts of
+    """log p(x) of a linear-Gaussian state-space model for every sequence (Kalman filter) with the adjoint
+    of the filter's own steps as gradient, ONE launch (pa_gaussian_hmm_fwd_bwd).  Arguments in the layouts of
     kernels.gaussian_hmm_fwd_bwd."""
 
     @staticmethod
