@@ -958,6 +958,32 @@ int pa_gaussian_hmm_sample(int dtype, const void* m0, int64_t m0_stride_batch, c
                            int64_t T, int64_t hidden, int64_t obs, int64_t S, const void* eps, void* z, void* maps_c,
                            void* maps_G, void* maps_L, void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gaussian_hmm_smooth.hip: the smoothed marginals of that model given all the data -----------------------
+ * E[z_t | x_1..T], Cov[z_t | x_1..T] and the lag-one Cov[z_t, z_{t+1} | x_1..T] of every step (what the reference's
+ * users rebuild from sequential_gaussian_filter_sample, pyro/ops/gaussian.py:600) in ONE launch on the caller's stream,
+ * one wave per sequence.  Parameters, strides and x as for pa_gaussian_hmm_fwd_bwd.  Forward: the same Kalman filter;
+ * backward the Rauch-Tung-Striebel recursion, with the states as columns, from ms_T = m_T, Ps_T = sym(P_T):
+ *   G = P_{t-1} F (P^p)^-1,   ms_{t-1} = m_{t-1} + G (ms_t - m^p),   Ps_{t-1} = sym(P_{t-1} + G (Ps_t - P^p) G^T),
+ *   X_{t-1} = G Ps_t = Cov(z_{t-1}, z_t | x),   t = T..2
+ * (the subtraction form: nothing is factorised, so Ps need not stay positive definite for the recursion to go on).
+ *   mean [B, T, hidden], cov [B, T, hidden, hidden], contiguous; z_0 is not included.
+ *   cross [B, T - 1, hidden, hidden] contiguous, cross[b, t] = Cov(z_t, z_{t+1}) with rows z_t and columns z_{t+1}
+ *     (0-based); may be NULL: the cross covariances are then not formed.  With T = 1 it is empty and not touched.
+ * A sequence with a non-positive pivot in the filter, in the Cholesky factor of a P^p or in the Q of a step the sweep
+ * visits (t = 2..T; checked for its pivots alone; P0 is not) gets NaN for all three outputs; other sequences are
+ * untouched.  No atomics, every element stored by one lane: bit-reproducible.
+ * hidden or obs > 16: PA_ERR_UNSUPPORTED.  B = 0: PA_OK without a launch.
+ * workspace: pa_gaussian_hmm_smooth_workspace(...) bytes -- B T (hidden + hidden^2) elements of filtered moments. */
+size_t pa_gaussian_hmm_smooth_workspace(int dtype, int64_t B, int64_t T, int64_t hidden, int64_t obs);
+int pa_gaussian_hmm_smooth(int dtype, const void* m0, int64_t m0_stride_batch, const void* P0,
+                           int64_t P0_stride_batch, const void* F, int64_t F_stride_batch, int64_t F_stride_step,
+                           const void* q, int64_t q_stride_batch, int64_t q_stride_step, const void* Q,
+                           int64_t Q_stride_batch, int64_t Q_stride_step, const void* H, int64_t H_stride_batch,
+                           int64_t H_stride_step, const void* r, int64_t r_stride_batch, int64_t r_stride_step,
+                           const void* R, int64_t R_stride_batch, int64_t R_stride_step, const void* x, int64_t B,
+                           int64_t T, int64_t hidden, int64_t obs, void* mean, void* cov, void* cross,
+                           void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* ---- csrc/gaussian_hmm_draw.hip: forward draws of that model, sample paths of x (and z) from the prior ------------
  * Replaces GaussianHMM.rsample (pyro/distributions/hmm.py:584-594 over sequential_gaussian_filter_sample,
  * pyro/ops/gaussian.py:600, then Gaussian.left_condition(z).rsample(): the parallel-scan filter with its tape and as

@@ -333,6 +333,12 @@ _SIGNATURES = {
                                + [c_void_p, c_int64, c_int64, c_int64, c_int64]                   # x, B T hidden obs
                                + [c_int64, c_void_p, c_void_p] + [c_void_p] * 3                   # S eps z, the maps
                                + [c_void_p, c_size_t, c_void_p]),
+    "pa_gaussian_hmm_smooth_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64]),
+    "pa_gaussian_hmm_smooth": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64]               # m0, P0
+                               + [c_void_p, c_int64, c_int64] * 6                                 # F q Q H r R
+                               + [c_void_p, c_int64, c_int64, c_int64, c_int64]                   # x, B T hidden obs
+                               + [c_void_p] * 3                                                   # mean, cov, cross
+                               + [c_void_p, c_size_t, c_void_p]),
     "pa_gaussian_hmm_draw_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64]),
     "pa_gaussian_hmm_draw": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64]                 # m0, P0
                              + [c_void_p, c_int64, c_int64] * 6                                   # F q Q H r R

@@ -487,6 +487,33 @@ std::tuple<at::Tensor, std::vector<at::Tensor>> gaussian_hmm_sample(
   return {z, maps};
 }
 
+// the smoothed marginals of that model's states given all the data in one launch: Kalman filter, then the
+// Rauch-Tung-Striebel sweep.  Layouts as kernels.gaussian_hmm_smooth: the parameters and x as above -> mean [B, T, h],
+// cov [B, T, h, h] and, with need_cross, [cross [B, T - 1, h, h]] with cross[b, t] = Cov(z_t, z_{t+1} | x) (empty
+// without)
+std::tuple<at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian_hmm_smooth(
+    const at::Tensor& m0, const at::Tensor& P0, const at::Tensor& trans, const at::Tensor& trans_loc,
+    const at::Tensor& trans_cov, const at::Tensor& obs, const at::Tensor& obs_loc, const at::Tensor& obs_cov,
+    const at::Tensor& x, bool need_cross) {
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const GhmmLayout l = gaussian_hmm_layout(p, x);
+  const int64_t B = l.B, T = l.T, h = l.h, o = l.o;
+  const int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss;
+  const auto opt = x.options();
+  at::Tensor mean = at::empty({B, T, h}, opt), cov = at::empty({B, T, h, h}, opt);
+  std::vector<at::Tensor> cross;
+  if (need_cross) cross = {at::empty({B, T - 1, h, h}, opt)};
+  const size_t ws_bytes = pa_gaussian_hmm_smooth_workspace(l.dt, B, T, h, o);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, opt.dtype(at::kByte));
+  check(pa_gaussian_hmm_smooth(l.dt, m0.data_ptr(), sb[0], P0.data_ptr(), sb[1], trans.data_ptr(), sb[2], ss[2],
+                               trans_loc.data_ptr(), sb[3], ss[3], trans_cov.data_ptr(), sb[4], ss[4], obs.data_ptr(),
+                               sb[5], ss[5], obs_loc.data_ptr(), sb[6], ss[6], obs_cov.data_ptr(), sb[7], ss[7],
+                               x.data_ptr(), B, T, h, o, mean.data_ptr(), cov.data_ptr(),
+                               need_cross ? cross[0].data_ptr() : nullptr, ws.data_ptr(), ws_bytes, current_stream()),
+        "gaussian_hmm_smooth");
+  return {mean, cov, cross};
+}
+
 // forward draws of that model in two launches (pyro/distributions/hmm.py:584-594 GaussianHMM.rsample over
 // pyro/ops/gaussian.py:600 sequential_gaussian_filter_sample and Gaussian.left_condition(z).rsample()).  Layouts as
 // kernels.gaussian_hmm_draw: the parameters as above, T steps, the standard normal eps0 [S, B, h], eps_z [S, B, T, h],
@@ -705,6 +732,8 @@ TORCH_LIBRARY(pyro_amd, m) {
         "Tensor filter_cov, Tensor[] grads)");
   m.def("gaussian_hmm_sample(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, Tensor x, Tensor eps, bool need_maps) -> (Tensor z, Tensor[] maps)");
+  m.def("gaussian_hmm_smooth(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
+        "Tensor obs_loc, Tensor obs_cov, Tensor x, bool need_cross) -> (Tensor mean, Tensor cov, Tensor[] cross)");
   m.def("gaussian_hmm_draw(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, int T, Tensor eps0, Tensor eps_z, Tensor eps_x, bool need_states) -> "
         "(Tensor x, Tensor[] states)");
@@ -738,6 +767,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("logchain_decode", &logchain_decode);
   m.impl("gaussian_hmm", &gaussian_hmm);
   m.impl("gaussian_hmm_sample", &gaussian_hmm_sample);
+  m.impl("gaussian_hmm_smooth", &gaussian_hmm_smooth);
   m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);

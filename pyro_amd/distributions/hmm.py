@@ -14,7 +14,9 @@ GaussianHMM: linear-Gaussian state-space model (reference: pyro/distributions/hm
 eliminates time with sequential_gaussian_tensordot (O(log T) rounds of batched Gaussian contractions); here
 log_prob is ONE launch of the Kalman filter kernel (pa_gaussian_hmm_fwd_bwd), whose backward pass -- the adjoint
 of the filter's own steps -- hands back the gradient with respect to every parameter and the data;
-rsample_posterior is the same filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample); rsample factors every distinct covariance once
+rsample_posterior is the same filter followed by a backward-sampling sweep (pa_gaussian_hmm_sample); smooth is the
+same filter followed by the Rauch-Tung-Striebel sweep, the smoothed marginals of every state in ONE launch
+(pa_gaussian_hmm_smooth); rsample factors every distinct covariance once
 and runs one lane per sample path (pa_gaussian_hmm_draw).  Whatever the kernels do
 not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
 the plain-torch sequential filter of this file, differentiated by autograd.
@@ -272,6 +274,51 @@ def _backward_sample(c, G, L, eps):
     return torch.stack(out[::-1], dim=-2)
 
 
+def _rts_smoother(m0, P0, F, q, Q, H, r, R, x):
+    """The smoothed marginals of z_1..z_T given x in plain torch ops, with the states written as columns.  Arguments
+    as for _kalman_filter -> (mean [..., T, h], cov [..., T, h, h], cross [..., T - 1, h, h] with cross_t =
+    Cov(z_t, z_{t+1} | x), rows z_t).  The same arithmetic as csrc/gaussian_hmm_smooth.hip: the filter above keeps
+    (m_t, P_t); ms_T = m_T, Ps_T = sym(P_T); for t = T..2, with m^p, P^p predicted from (m_{t-1}, P_{t-1}) as the
+    filter does and P^p = L L^T,
+        G = P_{t-1} F (P^p)^-1,   cross_{t-1} = G Ps_t,   ms_{t-1} = m_{t-1} + G (ms_t - m^p),
+        Ps_{t-1} = sym(P_{t-1} + (G (Ps_t - P^p)) G^T)
+    -- the subtraction form: nothing is factorised from Ps, so it need not stay positive definite for the recursion
+    to go on, and in float32 it is as accurate as the Joseph form of _backward_sample_maps or better.  An element
+    with a non-positive pivot, in the filter, in a factor of P^p or in the Q_t of a step the sweep visits (t = 2..T;
+    checked for its pivots alone, as the kernel does: F^T P F + Q is often positive definite where Q is not), is NaN
+    throughout.  P0 is never checked.  Differentiable."""
+    T = x.shape[-2]
+    kept = []
+    lp, _, _ = _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=kept)
+    bad = torch.isnan(lp)
+    batch = lp.shape
+    m, P = kept[-1]
+    h = m.shape[-1]
+    ms, Ps = m, 0.5 * (P + P.transpose(-1, -2))
+    means, covs, crosses = [ms.expand(batch + (h,))], [Ps.expand(batch + (h, h))], []
+    for t in range(T - 1, 0, -1):
+        m, P = kept[t - 1]
+        Ft, qt, Qt = _step(F, t, 2), _step(q, t, 1), _step(Q, t, 2)
+        mp = (m.unsqueeze(-2) @ Ft).squeeze(-2) + qt
+        FtP = Ft.transpose(-1, -2) @ P
+        Pp = FtP @ Ft + Qt
+        Pp = 0.5 * (Pp + Pp.transpose(-1, -2))
+        Lp, info = torch.linalg.cholesky_ex(Pp)
+        bad = (info > 0) | (torch.linalg.cholesky_ex(Qt)[1] > 0) | bad          # (Q_t: for its pivots alone)
+        G = torch.cholesky_solve(FtP, Lp).transpose(-1, -2)
+        crosses.append((G @ Ps).expand(batch + (h, h)))
+        ms = m + (G @ (ms - mp).unsqueeze(-1)).squeeze(-1)
+        Ps = P + (G @ (Ps - Pp)) @ G.transpose(-1, -2)
+        Ps = 0.5 * (Ps + Ps.transpose(-1, -2))
+        means.append(ms.expand(batch + (h,)))
+        covs.append(Ps.expand(batch + (h, h)))
+    mean, cov = (torch.stack(v[::-1], dim=len(batch)) for v in (means, covs))
+    cross = torch.stack(crosses[::-1], dim=len(batch)) if crosses else cov.new_zeros(batch + (0, h, h))
+    nan = mean.new_full((), float("nan"))
+    return (torch.where(bad[..., None, None], nan, mean), torch.where(bad[..., None, None, None], nan, cov),
+            torch.where(bad[..., None, None, None], nan, cross))
+
+
 class GaussianHMM(TorchDistribution):
     """Hidden Markov model with Gaussian initial, transition and observation distributions (reference:
     pyro/distributions/hmm.py:434-741), the generative model
@@ -292,6 +339,10 @@ class GaussianHMM(TorchDistribution):
 
     ``rsample_posterior`` draws the whole latent path given the data: two launches (csrc/gaussian_hmm_sample.hip) for
     the same tensors when nothing needs a gradient, the backward-sampling loop of this module otherwise.
+
+    ``smooth`` gives the smoothed marginals of every latent state given all the data -- mean, covariance and the
+    lag-one cross covariance: ONE launch (csrc/gaussian_hmm_smooth.hip) for the same tensors when nothing needs a
+    gradient, the Rauch-Tung-Striebel loop of this module, differentiable, otherwise.
 
     ``rsample`` draws sample paths of the observations, and with ``prefix_condition(data).rsample(...)`` forecasts:
     again two launches (csrc/gaussian_hmm_draw.hip) for the same tensors when nothing needs a gradient, after the
@@ -460,6 +511,37 @@ class GaussianHMM(TorchDistribution):
             return z.reshape(shape)
         c, G, L = _backward_sample_maps(*self._parts, value)
         return _backward_sample(c, G, L, noise).expand(shape)
+
+    def smooth(self, value, cross=False):
+        """The smoothed marginals of the latent states given ALL the observations ``value`` [..., T, obs_dim]:
+        ``(mean, cov)`` with ``mean[..., t, :] = E[z_t | x_1..T]`` of shape ``batch + (T, hidden_dim)`` and
+        ``cov[..., t, :, :] = Cov[z_t | x_1..T]`` of shape ``batch + (T, hidden_dim, hidden_dim)``, ``batch`` the
+        broadcast of ``batch_shape`` and ``value.shape[:-2]``; with ``cross=True`` ``(mean, cov, cross)``, where
+        ``cross[..., t, :, :] = Cov[z_t, z_{t+1} | x_1..T]`` (rows ``z_t``, columns ``z_{t+1}``) has shape
+        ``batch + (T - 1, hidden_dim, hidden_dim)``.  The initial state ``z_0`` is not included, as in
+        ``rsample_posterior``.  These are a state estimate with its error band, and the E-step of EM.  (The
+        reference's class has no such method.)
+
+        The Rauch-Tung-Striebel recursion after the Kalman filter: ``ms_T = m_T``, ``Ps_T = sym(P_T)`` and, with the
+        states as columns, ``G = P_{t-1} F (P^p)^-1``, ``ms_{t-1} = m_{t-1} + G (ms_t - m^p)``,
+        ``Ps_{t-1} = sym(P_{t-1} + G (Ps_t - P^p) G^T)``, ``cross_{t-1} = G Ps_t``.
+
+        The routing is ``rsample_posterior``'s.  With grad mode on and a parameter or ``value`` requiring a gradient:
+        the torch route, differentiable in all of them (it also serves CPU tensors, dimensions over 16, other dtypes
+        and ``hmm.FUSED_GAUSSIAN_HMM = False``).  Otherwise device tensors within the kernel's limits take the ONE
+        launch of csrc/gaussian_hmm_smooth.hip and the result is DETACHED, like ``filter``'s.  A series with a
+        non-positive pivot, of the filter, of a predicted covariance or of a transition covariance the backward sweep
+        uses (steps 2..T), is NaN in all three."""
+        batch, T = self._check_value(value)
+        h = self.hidden_dim
+        needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in self._parts + (value,))
+        shapes = (batch + (T, h), batch + (T, h, h), batch + (T - 1, h, h))[:3 if cross else 2]
+        if not needs_grad and self._takes_kernel(value):
+            from .. import kernels
+            args = [t.detach() for t in self._kernel_inputs(value, batch, T)]
+            out = kernels.gaussian_hmm_smooth(*args, need_cross=cross)
+            return tuple(v.reshape(s) for v, s in zip(out, shapes))
+        return tuple(v.expand(s) for v, s in zip(_rts_smoother(*self._parts, value), shapes))
 
     def prefix_condition(self, data):
         """Given ``event_shape == (t + f, d)`` and ``data`` [..., t, d], the conditional distribution of the

@@ -930,6 +930,30 @@ def gaussian_hmm_sample(m0, P0, F, q, Q, H, r, R, x, eps, need_maps=False):
     return z, maps
 
 
+def gaussian_hmm_smooth(m0, P0, F, q, Q, H, r, R, x, need_cross=False):
+    """The smoothed marginals of that model's latent states given all the data x, Kalman filter and
+    Rauch-Tung-Striebel sweep in ONE launch (pa_gaussian_hmm_smooth).  Parameters and x in the layouts of
+    gaussian_hmm_fwd_bwd.  -> (mean [B, T, h] = E[z_t | x], cov [B, T, h, h] = Cov[z_t | x], cross): ``cross``
+    [B, T - 1, h, h] with ``need_cross``, cross[b, t] = Cov(z_t, z_{t+1} | x) with rows z_t and columns z_{t+1}
+    (0-based; empty for T = 1), else None.  z_0 is not included.  With the states as columns, from ms_T = m_T,
+    Ps_T = sym(P_T): G = P_{t-1} F (P^p)^-1, ms_{t-1} = m_{t-1} + G (ms_t - m^p),
+    Ps_{t-1} = sym(P_{t-1} + G (Ps_t - P^p) G^T), cross_{t-1} = G Ps_t.  mean and cov do not depend on ``need_cross``.
+    A sequence with a non-positive pivot, of the filter, of a P^p or of the Q of a step t >= 2, gets NaN in all three.  Nothing here is
+    differentiable.  hidden or obs over GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    B, T, h, o, strides, _ = _gaussian_hmm_layout(params, x)
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, dtype=x.dtype, device=x.device)     # noqa: E731
+    mean, cov = new(B, T, h), new(B, T, h, h)
+    cross = new(B, T - 1, h, h) if need_cross else None
+    nbytes = lib.pa_gaussian_hmm_smooth_workspace(_dtype(x), B, T, h, o)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    args = _gaussian_hmm_args(params, x, strides, B, T, h, o)
+    args += [_ptr(mean), _ptr(cov), _ptr(cross), _ptr(ws), nbytes, _stream()]
+    check(lib.pa_gaussian_hmm_smooth(*args))
+    return mean, cov, cross
+
+
 def gaussian_hmm_draw(m0, P0, F, q, Q, H, r, R, T, eps0, eps_z, eps_x, need_states=False):
     """Forward draws of that model in two launches (pa_gaussian_hmm_draw): z_0 = m0 + L_0 e_0,
     z_t = z_{t-1} F_t + q_t + L_{Q,t} e_t, x_t = z_t H_t + r_t + L_{R,t} e'_t for t = 1..T, with L L^T the Cholesky

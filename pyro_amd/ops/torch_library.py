@@ -143,6 +143,13 @@ def _register():
         maps = [x.new_empty((B, T, h)), x.new_empty((B, T, h, h)), x.new_empty((B, T, h, h))] if need_maps else []
         return x.new_empty((eps.shape[0], B, T, h)), maps
 
+    @lib.register_fake("pyro_amd::gaussian_hmm_smooth")
+    def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, x, need_cross):
+        B, T, _o = x.shape
+        h = m0.shape[-1]
+        cross = [x.new_empty((B, T - 1, h, h))] if need_cross else []
+        return x.new_empty((B, T, h)), x.new_empty((B, T, h, h)), cross
+
     @lib.register_fake("pyro_amd::gaussian_hmm_draw")
     def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, T, eps0, eps_z, eps_x, need_states):
         S, B, h = eps0.shape
@@ -630,4 +637,5 @@ def registered_ops():
 # the typed C++ ops of csrc/torch_ops.cpp beside the GLM site's (round 6): real argument lists, loadable from C++
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
-             "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw")
+             "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw",
+             "gaussian_hmm_smooth")
