@@ -930,6 +930,30 @@ int pa_gaussian_hmm_fwd_bwd(int dtype, const void* m0, int64_t m0_stride_batch, 
                             void* grad_H, void* grad_r, void* grad_R, void* grad_x, void* workspace,
                             size_t workspace_bytes, pa_stream_t stream);
 
+/* The Student-t variant of the same kernel: every covariance of that model divided by one s ~ Gamma(concentration,
+ * rate) per sequence (GammaGaussianHMM.log_prob / .filter, pyro/distributions/hmm.py:744-940), one launch.
+ * concentration, rate: [B | 1] of ``dtype``, batch stride 0 (shared) or 1.  Everything from m0 through obs as above.
+ *   quad[b]   = sum_t |L_t^-1 y_t|^2,   logdet[b] = sum_t sum log diag L_t   of the filter at unit scale (S_t = L_t L_t^T),
+ *   so that with n = T obs
+ *     log_prob[b] = lgamma(a + n/2) - lgamma(a) + a log b - (a + n/2) log(b + quad/2) - logdet - n/2 log(2 pi)
+ *   and the posterior of s is Gamma(a + n/2, b + quad/2); filter_mean / filter_cov: the filtered moments at unit scale.
+ *   grad_* (all nine or none): d log_prob[b] / d input, laid out as above -- the adjoint sweep of the Gaussian model at
+ *     covariances divided by w = (a + n/2) / (b + quad/2), the covariance gradients multiplied by 1 / w.  The caller
+ *     has  d/da = digamma(a + n/2) - digamma(a) + log b - log(b + quad/2)  and  d/db = a / b - w.
+ * NaN convention, limits and workspace (pa_gaussian_hmm_workspace) as above; quad and logdet are NaN where log_prob was. */
+int pa_gamma_gaussian_hmm_fwd_bwd(int dtype, const void* concentration, int64_t concentration_stride_batch,
+                                  const void* rate, int64_t rate_stride_batch, const void* m0,
+                                  int64_t m0_stride_batch, const void* P0, int64_t P0_stride_batch, const void* F,
+                                  int64_t F_stride_batch, int64_t F_stride_step, const void* q, int64_t q_stride_batch,
+                                  int64_t q_stride_step, const void* Q, int64_t Q_stride_batch, int64_t Q_stride_step,
+                                  const void* H, int64_t H_stride_batch, int64_t H_stride_step, const void* r,
+                                  int64_t r_stride_batch, int64_t r_stride_step, const void* R, int64_t R_stride_batch,
+                                  int64_t R_stride_step, const void* x, int64_t B, int64_t T, int64_t hidden,
+                                  int64_t obs, void* quad, void* logdet, void* filter_mean, void* filter_cov,
+                                  void* grad_m0, void* grad_P0, void* grad_F, void* grad_q, void* grad_Q, void* grad_H,
+                                  void* grad_r, void* grad_R, void* grad_x, void* workspace, size_t workspace_bytes,
+                                  pa_stream_t stream);
+
 /* ---- csrc/gaussian_hmm_sample.hip: draws of the latent path of that model given the data -------------------------
  * Replaces GaussianHMM.rsample_posterior (pyro/distributions/hmm.py:596-604 over sequential_gaussian_filter_sample,
  * pyro/ops/gaussian.py:600: a parallel-scan forward filter with a tape, then as many rounds of conditional draws)

@@ -327,6 +327,12 @@ _SIGNATURES = {
                                 + [c_void_p, c_int64, c_int64, c_int64, c_int64]                  # x, B T hidden obs
                                 + [c_void_p] * 3 + [c_void_p] * 9                                 # outputs, gradients
                                 + [c_void_p, c_size_t, c_void_p]),
+    "pa_gamma_gaussian_hmm_fwd_bwd": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64]        # concentration, rate
+                                      + [c_void_p, c_int64, c_void_p, c_int64]                    # m0, P0
+                                      + [c_void_p, c_int64, c_int64] * 6                          # F q Q H r R
+                                      + [c_void_p, c_int64, c_int64, c_int64, c_int64]            # x, B T hidden obs
+                                      + [c_void_p] * 4 + [c_void_p] * 9                           # outputs, gradients
+                                      + [c_void_p, c_size_t, c_void_p]),
     "pa_gaussian_hmm_sample_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64]),
     "pa_gaussian_hmm_sample": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64]               # m0, P0
                                + [c_void_p, c_int64, c_int64] * 6                                 # F q Q H r R

@@ -35,6 +35,17 @@
 // side each.  The next step's x, heterogeneous parameters and (backward) filtered moments are loaded into registers
 // while the current step computes and are written to LDS at the top of the next step.
 //
+// The Student-t variant (template parameter ST; pa_gamma_gaussian_hmm_fwd_bwd, reference: GammaGaussianHMM.log_prob,
+// pyro/distributions/hmm.py:744-940): every covariance of the model divided by one s ~ Gamma(a, b) per series.  The
+// filter's means, gains and P / P^p ratios do not depend on s, so the forward pass is the same filter at unit scale; it
+// keeps  quad = sum_t |v_t|^2  and  logdet = sum_t sum log diag L_t  apart (both in double) and writes them instead of
+// log_prob, which the caller forms:  lgamma(a + n/2) - lgamma(a) + a log b - (a + n/2) log(b + quad/2) - logdet -
+// n/2 log 2 pi,  n = T obs.  With w = (a + n/2) / (b + quad/2) held constant, the gradient with respect to m0, F, q,
+// H, r, x is that of the GAUSSIAN model at P0 / w, Q_t / w, R_t / w, and with respect to P0, Q_t, R_t it is 1 / w times
+// that model's with respect to its scaled covariance.  So the wave forms w from its series' a, b and runs the sweep
+// below unchanged: P0, Q, R and the filtered covariances read back from the workspace are multiplied by 1 / w on their
+// way into LDS, the three covariance gradients on their way out.  d/da and d/db are closed forms of quad, the caller's.
+//
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage), one wave of 64 lanes per block:
 //     instantiation    VGPRs      SGPRs  scratch   LDS bytes   waves / SIMD
 //     <float , 8>      135        106    0         5832        3
@@ -42,6 +53,12 @@
 //     <double, 8>      168        106    0         11664       2
 //     <double, 16>     256 + 60   106    0         42768       1
 // (+ n: accumulation registers the 16-wide instantiations use as spill space; nothing goes to scratch memory)
+// With the Student-t template parameter the four Gaussian instantiations <., ., false> compile to the same figures
+// (135 / 256 + 5 / 168 / 256 + 60 VGPRs, 106 SGPRs, scratch 0, the same LDS); the Student-t ones:
+//     <float , 8 , true>   161        106    0         5832        3
+//     <float , 16, true>   256 + 8    106    0         21384       1
+//     <double, 8 , true>   170        106    0         11664       2
+//     <double, 16, true>   256 + 61   106    0         42768       1
 #include <limits>
 
 #include "common.h"
@@ -53,9 +70,15 @@ struct GhmmArgs {
   GhModel m;
   int grads;
   void *lp, *fm, *fP, *g_m0, *g_P0, *g_F, *g_q, *g_Q, *g_H, *g_r, *g_R, *g_x, *ws;
+  // the Student-t variant alone: the Gamma's concentration and rate ([B | 1], batch stride 0 or 1); it writes quad
+  // and logdet instead of lp
+  const void *ga, *gb;
+  int64_t ga_sb, gb_sb;
+  void *quad, *logdet;
 };
 
-template <typename T, int MD>
+// ST: the Student-t variant (see the top of the file)
+template <typename T, int MD, bool ST>
 __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   constexpr int LD = MD + 1, MS = MD * LD, EPL = MD * MD / 64;
   constexpr int NMAT = 19, NVEC = 11;
@@ -94,13 +117,26 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   // ---- forward: the Kalman filter ----------------------------------------------------------------------------
   f.start();
   double lp = 0.0;               // (in double also for float32: T terms of one sign, |log_prob| grows with T)
+  double quad = 0.0, lds = 0.0;  // (ST: the two halves of lp kept apart)
   const T half_log_2pi_o = T(0.91893853320467274178) * T(o);
   for (int t = 0; t < Tn; ++t) {
     const T logdet = f.step(t, a.grads ? wsb + (int64_t)t * wstep : nullptr);
-    lp += (double)(T(-0.5) * f.sc[0] - logdet - half_log_2pi_o);
+    if constexpr (ST) {
+      quad += (double)f.sc[0];
+      lds += (double)logdet;
+    } else {
+      lp += (double)(T(-0.5) * f.sc[0] - logdet - half_log_2pi_o);
+    }
   }
   __syncthreads();
-  if (lane == 0) ((T*)a.lp)[b] = bad ? NaN : (T)lp;
+  if constexpr (ST) {
+    if (lane == 0) {
+      ((T*)a.quad)[b] = bad ? NaN : (T)quad;
+      ((T*)a.logdet)[b] = bad ? NaN : (T)lds;
+    }
+  } else {
+    if (lane == 0) ((T*)a.lp)[b] = bad ? NaN : (T)lp;
+  }
   if (a.fm && lane < h) ((T*)a.fm)[b * h + lane] = bad ? NaN : vm[lane];
   if (a.fP) {
 #pragma unroll
@@ -176,6 +212,19 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   T* const vhw = ve;             // H w
   T* const vrho = vu;            // rho = w - K^T mu
 
+  // ST: the sweep is the Gaussian model's at P0 / w, Q_t / w, R_t / w with w = (a + n / 2) / (b + quad / 2) held
+  // constant; iw = 1 / w scales those three and the filtered covariances on their way into LDS and the three
+  // covariance gradients on their way out.  (A lane scales the elements it wrote itself: no barrier in between.)
+  T iw = T(1);
+  if constexpr (ST) {
+    const double ca = ((const T*)a.ga)[b * a.ga_sb], cb = ((const T*)a.gb)[b * a.gb_sb];
+    iw = (T)((cb + 0.5 * quad) / (ca + 0.5 * (double)Tn * (double)o));
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {          // the time-homogeneous ones: in LDS since the first step of the filter
+      if (!a.m.Q_ss && lhh[k] >= 0) sQ[lhh[k]] *= iw;
+      if (!a.m.R_ss && loo[k] >= 0) sR[loo[k]] *= iw;
+    }
+  }
   if (lane < h) vmu[lane] = T(0);
 #pragma unroll
   for (int k = 0; k < EPL; ++k)
@@ -210,8 +259,13 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
     f.commit_params(false, true);
     if (lane < h) vm[lane] = f.pm;
 #pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      if (lhh[k] >= 0) sP[lhh[k]] = f.pP[k];
+    for (int k = 0; k < EPL; ++k) {
+      if (lhh[k] >= 0) sP[lhh[k]] = ST ? f.pP[k] * iw : f.pP[k];
+      if constexpr (ST) {
+        if (a.m.Q_ss && lhh[k] >= 0) sQ[lhh[k]] = f.pQ[k] * iw;
+        if (a.m.R_ss && loo[k] >= 0) sR[loo[k]] = f.pR[k] * iw;
+      }
+    }
     if (t > 0) {
       f.load_params(t - 1, false, true);
       load_filtered(t - 1);
@@ -310,7 +364,7 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
     for (int k = 0; k < EPL; ++k) {
       const int e = lane + 64 * k;
       if (loo[k] >= 0) {                                         // d/dR = Sigma
-        const T s = sSg[loo[k]];
+        const T s = ST ? sSg[loo[k]] * iw : sSg[loo[k]];
         if (a.m.R_ss) gR[(int64_t)t * oo + e] = s; else aR[k] += s;
       }
       if (lho[k] >= 0) {
@@ -338,6 +392,7 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
         for (int i = 0; i < o; ++i)
           s += ((AT)sHS[j * LD + i] - sMK[j * LD + i]) * sH[c * LD + i] - (AT)sMK[c * LD + i] * sH[j * LD + i];
         sLa[lhh[k]] = s;
+        if constexpr (ST) s *= iw;
         if (a.m.Q_ss) gQ[(int64_t)t * hh + e] = s; else aQ[k] += s;
       }
     }
@@ -395,9 +450,57 @@ __global__ __launch_bounds__(64) void gaussian_hmm_kernel(const GhmmArgs a) {
   if (lane < h) gm0[lane] = vmu[lane];
 #pragma unroll
   for (int k = 0; k < EPL; ++k)
-    if (lhh[k] >= 0) gP0[lane + 64 * k] = sMa[lhh[k]];
+    if (lhh[k] >= 0) gP0[lane + 64 * k] = ST ? sMa[lhh[k]] * iw : sMa[lhh[k]];
   check_pivots(sP, h, lhh);
   if (bad) fill_nan();
+}
+
+// what the two entry points share: the checks, the workspace and the launch (``who`` names the entry point in errors)
+static int ghmm_launch(const char* who, bool student, int dtype, GhmmArgs& a, int64_t B, int64_t T, int64_t hidden,
+                       int64_t obs, size_t workspace_bytes, pa_stream_t stream) {
+  const GhModel& m = a.m;
+  PA_REQUIRE(dtype == PA_F32 || dtype == PA_F64, "%s: bad dtype %d", who, dtype);
+  PA_REQUIRE(B >= 0 && T >= 1 && hidden >= 1 && obs >= 1, "%s: bad shape B=%lld T=%lld hidden=%lld obs=%lld", who,
+             (long long)B, (long long)T, (long long)hidden, (long long)obs);
+  if (hidden > GH_MAXHIDDEN || obs > GH_MAXOBS)
+    return fail(PA_ERR_UNSUPPORTED, "%s: hidden=%lld obs=%lld over the limit of %d / %d", who, (long long)hidden,
+                (long long)obs, GH_MAXHIDDEN, GH_MAXOBS);
+  PA_REQUIRE(B < (int64_t(1) << 31) && T < (int64_t(1) << 31), "%s: shape too large", who);
+  if (B == 0) return PA_OK;
+  PA_REQUIRE(m.m0 && m.P0 && m.F && m.q && m.Q && m.H && m.r && m.R && m.x, "%s: NULL pointer", who);
+  if (student) {
+    PA_REQUIRE(a.ga && a.gb && a.quad && a.logdet, "%s: NULL pointer", who);
+    PA_REQUIRE((a.ga_sb == 0 || a.ga_sb == 1) && (a.gb_sb == 0 || a.gb_sb == 1),
+               "%s: concentration and rate are [B | 1], batch stride 0 or 1", who);
+  } else {
+    PA_REQUIRE(a.lp, "%s: NULL pointer", who);
+  }
+  PA_REQUIRE((a.fm == nullptr) == (a.fP == nullptr), "%s: filter mean and covariance go together", who);
+  const int ng = (a.g_m0 != nullptr) + (a.g_P0 != nullptr) + (a.g_F != nullptr) + (a.g_q != nullptr) +
+                 (a.g_Q != nullptr) + (a.g_H != nullptr) + (a.g_r != nullptr) + (a.g_R != nullptr) +
+                 (a.g_x != nullptr);
+  PA_REQUIRE(ng == 0 || ng == 9, "%s: all nine gradient pointers or none", who);
+  PA_REQUIRE(m.m0_sb >= 0 && m.P0_sb >= 0 && m.F_sb >= 0 && m.F_ss >= 0 && m.q_sb >= 0 && m.q_ss >= 0 &&
+                 m.Q_sb >= 0 && m.Q_ss >= 0 && m.H_sb >= 0 && m.H_ss >= 0 && m.r_sb >= 0 && m.r_ss >= 0 &&
+                 m.R_sb >= 0 && m.R_ss >= 0,
+             "%s: negative stride", who);
+  const size_t need = pa_gaussian_hmm_workspace(dtype, B, T, hidden, obs, ng != 0);
+  PA_REQUIRE(need == 0 || (a.ws && workspace_bytes >= need), "%s: workspace too small", who);
+  a.grads = ng != 0;
+  hipStream_t s = as_stream(stream);
+  const bool small = hidden <= 8 && obs <= 8;
+#define PA_GH_LAUNCH(T_, MD_)                                                                             \
+  do {                                                                                                    \
+    if (student) hipLaunchKernelGGL((gaussian_hmm_kernel<T_, MD_, true>), dim3((unsigned)B), dim3(64), 0, s, a); \
+    else hipLaunchKernelGGL((gaussian_hmm_kernel<T_, MD_, false>), dim3((unsigned)B), dim3(64), 0, s, a); \
+  } while (0)
+  if (dtype == PA_F32) {
+    if (small) PA_GH_LAUNCH(float, 8); else PA_GH_LAUNCH(float, 16);
+  } else {
+    if (small) PA_GH_LAUNCH(double, 8); else PA_GH_LAUNCH(double, 16);
+  }
+#undef PA_GH_LAUNCH
+  return check_launch("gaussian_hmm_kernel");
 }
 
 }  // namespace pa
@@ -420,45 +523,38 @@ int pa_gaussian_hmm_fwd_bwd(int dtype, const void* m0, int64_t m0_stride_batch, 
                             void* filter_cov, void* grad_m0, void* grad_P0, void* grad_F, void* grad_q, void* grad_Q,
                             void* grad_H, void* grad_r, void* grad_R, void* grad_x, void* workspace,
                             size_t workspace_bytes, pa_stream_t stream) {
-  PA_REQUIRE(dtype == PA_F32 || dtype == PA_F64, "gaussian_hmm: bad dtype %d", dtype);
-  PA_REQUIRE(B >= 0 && T >= 1 && hidden >= 1 && obs >= 1, "gaussian_hmm: bad shape B=%lld T=%lld hidden=%lld obs=%lld",
-             (long long)B, (long long)T, (long long)hidden, (long long)obs);
-  if (hidden > pa::GH_MAXHIDDEN || obs > pa::GH_MAXOBS)
-    return pa::fail(PA_ERR_UNSUPPORTED, "gaussian_hmm: hidden=%lld obs=%lld over the limit of %d / %d",
-                    (long long)hidden, (long long)obs, pa::GH_MAXHIDDEN, pa::GH_MAXOBS);
-  PA_REQUIRE(B < (int64_t(1) << 31) && T < (int64_t(1) << 31), "gaussian_hmm: shape too large");
-  if (B == 0) return PA_OK;
-  PA_REQUIRE(m0 && P0 && F && q && Q && H && r && R && x && log_prob, "gaussian_hmm: NULL pointer");
-  PA_REQUIRE((filter_mean == nullptr) == (filter_cov == nullptr), "gaussian_hmm: filter mean and covariance go together");
-  const int ng = (grad_m0 != nullptr) + (grad_P0 != nullptr) + (grad_F != nullptr) + (grad_q != nullptr) +
-                 (grad_Q != nullptr) + (grad_H != nullptr) + (grad_r != nullptr) + (grad_R != nullptr) +
-                 (grad_x != nullptr);
-  PA_REQUIRE(ng == 0 || ng == 9, "gaussian_hmm: all nine gradient pointers or none");
-  PA_REQUIRE(m0_stride_batch >= 0 && P0_stride_batch >= 0 && F_stride_batch >= 0 && F_stride_step >= 0 &&
-                 q_stride_batch >= 0 && q_stride_step >= 0 && Q_stride_batch >= 0 && Q_stride_step >= 0 &&
-                 H_stride_batch >= 0 && H_stride_step >= 0 && r_stride_batch >= 0 && r_stride_step >= 0 &&
-                 R_stride_batch >= 0 && R_stride_step >= 0,
-             "gaussian_hmm: negative stride");
-  const size_t need = pa_gaussian_hmm_workspace(dtype, B, T, hidden, obs, ng != 0);
-  PA_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "gaussian_hmm: workspace too small");
   pa::GhmmArgs a{{m0, P0, F, q, Q, H, r, R, x,
                   m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
                   Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
                   R_stride_batch, R_stride_step, (int)T, (int)hidden, (int)obs},
-                 ng != 0,
+                 0,
                  log_prob, filter_mean, filter_cov, grad_m0, grad_P0, grad_F, grad_q, grad_Q, grad_H, grad_r, grad_R,
-                 grad_x, workspace};
-  hipStream_t s = pa::as_stream(stream);
-  const bool small = hidden <= 8 && obs <= 8;
-#define PA_GH_LAUNCH(T_, MD_) \
-  hipLaunchKernelGGL((pa::gaussian_hmm_kernel<T_, MD_>), dim3((unsigned)B), dim3(64), 0, s, a)
-  if (dtype == PA_F32) {
-    if (small) PA_GH_LAUNCH(float, 8); else PA_GH_LAUNCH(float, 16);
-  } else {
-    if (small) PA_GH_LAUNCH(double, 8); else PA_GH_LAUNCH(double, 16);
-  }
-#undef PA_GH_LAUNCH
-  return pa::check_launch("gaussian_hmm_kernel");
+                 grad_x, workspace,
+                 nullptr, nullptr, 0, 0, nullptr, nullptr};
+  return pa::ghmm_launch("gaussian_hmm", false, dtype, a, B, T, hidden, obs, workspace_bytes, stream);
+}
+
+int pa_gamma_gaussian_hmm_fwd_bwd(int dtype, const void* concentration, int64_t concentration_stride_batch,
+                                  const void* rate, int64_t rate_stride_batch, const void* m0,
+                                  int64_t m0_stride_batch, const void* P0, int64_t P0_stride_batch, const void* F,
+                                  int64_t F_stride_batch, int64_t F_stride_step, const void* q, int64_t q_stride_batch,
+                                  int64_t q_stride_step, const void* Q, int64_t Q_stride_batch, int64_t Q_stride_step,
+                                  const void* H, int64_t H_stride_batch, int64_t H_stride_step, const void* r,
+                                  int64_t r_stride_batch, int64_t r_stride_step, const void* R, int64_t R_stride_batch,
+                                  int64_t R_stride_step, const void* x, int64_t B, int64_t T, int64_t hidden,
+                                  int64_t obs, void* quad, void* logdet, void* filter_mean, void* filter_cov,
+                                  void* grad_m0, void* grad_P0, void* grad_F, void* grad_q, void* grad_Q, void* grad_H,
+                                  void* grad_r, void* grad_R, void* grad_x, void* workspace, size_t workspace_bytes,
+                                  pa_stream_t stream) {
+  pa::GhmmArgs a{{m0, P0, F, q, Q, H, r, R, x,
+                  m0_stride_batch, P0_stride_batch, F_stride_batch, F_stride_step, q_stride_batch, q_stride_step,
+                  Q_stride_batch, Q_stride_step, H_stride_batch, H_stride_step, r_stride_batch, r_stride_step,
+                  R_stride_batch, R_stride_step, (int)T, (int)hidden, (int)obs},
+                 0,
+                 nullptr, filter_mean, filter_cov, grad_m0, grad_P0, grad_F, grad_q, grad_Q, grad_H, grad_r, grad_R,
+                 grad_x, workspace,
+                 concentration, rate, concentration_stride_batch, rate_stride_batch, quad, logdet};
+  return pa::ghmm_launch("gamma_gaussian_hmm", true, dtype, a, B, T, hidden, obs, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -454,6 +454,48 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gaussian
   return {log_prob, fm, fP, g};
 }
 
+// that model with every covariance divided by one s ~ Gamma(concentration, rate) per sequence, a jointly Student-t series
+// (pyro/distributions/hmm.py:744-940 GammaGaussianHMM.log_prob / .filter): the filter at unit scale and the adjoint sweep
+// in one launch.  concentration, rate [B | 1]; the rest as above -> quad [B], logdet [B] (log_prob = lgamma(a + n/2) -
+// lgamma(a) + a log b - (a + n/2) log(b + quad/2) - logdet - n/2 log(2 pi), n = T obs), the filtered moments at unit
+// scale and the nine gradients of that log_prob[b] with respect to m0 .. x
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<at::Tensor>> gamma_gaussian_hmm(
+    const at::Tensor& concentration, const at::Tensor& rate, const at::Tensor& m0, const at::Tensor& P0,
+    const at::Tensor& trans, const at::Tensor& trans_loc, const at::Tensor& trans_cov, const at::Tensor& obs,
+    const at::Tensor& obs_loc, const at::Tensor& obs_cov, const at::Tensor& x, bool need_grads) {
+  const at::Tensor* p[8] = {&m0, &P0, &trans, &trans_loc, &trans_cov, &obs, &obs_loc, &obs_cov};
+  const GhmmLayout l = gaussian_hmm_layout(p, x);
+  const int dt = l.dt;
+  const int64_t B = l.B, T = l.T, h = l.h, o = l.o;
+  const int64_t(&sb)[8] = l.sb, (&ss)[8] = l.ss, (&steps)[8] = l.steps;
+  for (const at::Tensor* t : {&concentration, &rate})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == x.scalar_type() && t->is_contiguous() && t->dim() == 1 &&
+                    (t->size(0) == 1 || t->size(0) == B),
+                "pyro_amd::gamma_gaussian_hmm: concentration and rate [B | 1] contiguous of x's dtype");
+  const auto opt = x.options();
+  at::Tensor quad = at::empty({B}, opt), logdet = at::empty({B}, opt), fm = at::empty({B, h}, opt),
+             fP = at::empty({B, h, h}, opt);
+  std::vector<at::Tensor> g;
+  if (need_grads) {
+    g = {at::empty({B, h}, opt), at::empty({B, h, h}, opt), at::empty({B, steps[2], h, h}, opt),
+         at::empty({B, steps[3], h}, opt), at::empty({B, steps[4], h, h}, opt), at::empty({B, steps[5], h, o}, opt),
+         at::empty({B, steps[6], o}, opt), at::empty({B, steps[7], o, o}, opt), at::empty({B, T, o}, opt)};
+  }
+  auto gp = [&](int i) { return need_grads ? g[i].data_ptr() : nullptr; };
+  const size_t ws_bytes = pa_gaussian_hmm_workspace(dt, B, T, h, o, need_grads ? 1 : 0);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes < 16 ? 16 : ws_bytes)}, opt.dtype(at::kByte));
+  check(pa_gamma_gaussian_hmm_fwd_bwd(dt, concentration.data_ptr(), concentration.size(0) == 1 ? 0 : 1, rate.data_ptr(),
+                                      rate.size(0) == 1 ? 0 : 1, m0.data_ptr(), sb[0], P0.data_ptr(), sb[1],
+                                      trans.data_ptr(), sb[2], ss[2], trans_loc.data_ptr(), sb[3], ss[3],
+                                      trans_cov.data_ptr(), sb[4], ss[4], obs.data_ptr(), sb[5], ss[5],
+                                      obs_loc.data_ptr(), sb[6], ss[6], obs_cov.data_ptr(), sb[7], ss[7], x.data_ptr(), B,
+                                      T, h, o, quad.data_ptr(), logdet.data_ptr(), fm.data_ptr(), fP.data_ptr(), gp(0),
+                                      gp(1), gp(2), gp(3), gp(4), gp(5), gp(6), gp(7), gp(8), ws.data_ptr(), ws_bytes,
+                                      current_stream()),
+        "gamma_gaussian_hmm");
+  return {quad, logdet, fm, fP, g};
+}
+
 // draws of that model's latent path given the data, forward filter and backward sample in two launches
 // (pyro/distributions/hmm.py:596-604 GaussianHMM.rsample_posterior over pyro/ops/gaussian.py:600
 // sequential_gaussian_filter_sample).  Layouts as kernels.gaussian_hmm_sample: the parameters and x as above, eps
@@ -730,6 +772,9 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("gaussian_hmm(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, Tensor x, bool need_grads) -> (Tensor log_prob, Tensor filter_mean, "
         "Tensor filter_cov, Tensor[] grads)");
+  m.def("gamma_gaussian_hmm(Tensor concentration, Tensor rate, Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, "
+        "Tensor trans_cov, Tensor obs, Tensor obs_loc, Tensor obs_cov, Tensor x, bool need_grads) -> (Tensor quad, "
+        "Tensor logdet, Tensor filter_mean, Tensor filter_cov, Tensor[] grads)");
   m.def("gaussian_hmm_sample(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, Tensor x, Tensor eps, bool need_maps) -> (Tensor z, Tensor[] maps)");
   m.def("gaussian_hmm_smooth(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
@@ -766,6 +811,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("logchain", &logchain);
   m.impl("logchain_decode", &logchain_decode);
   m.impl("gaussian_hmm", &gaussian_hmm);
+  m.impl("gamma_gaussian_hmm", &gamma_gaussian_hmm);
   m.impl("gaussian_hmm_sample", &gaussian_hmm_sample);
   m.impl("gaussian_hmm_smooth", &gaussian_hmm_smooth);
   m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);

@@ -20,6 +20,11 @@ same filter followed by the Rauch-Tung-Striebel sweep, the smoothed marginals of
 and runs one lane per sample path (pa_gaussian_hmm_draw).  Whatever the kernels do
 not take -- CPU tensors, hidden or obs dimension over 16, other dtypes, FUSED_GAUSSIAN_HMM = False -- goes through
 the plain-torch sequential filter of this file, differentiated by autograd.
+
+GammaGaussianHMM: that model with one Gamma-distributed precision multiplier shared by all its noise, a jointly
+Student-t series (reference: pyro/distributions/hmm.py:744-940).  log_prob is ONE launch of the Student-t variant of
+the same kernel (pa_gamma_gaussian_hmm_fwd_bwd): the filter at unit scale, then the adjoint sweep at covariances
+divided by the series' weight; the routing and the torch route are GaussianHMM's.
 """
 import math
 
@@ -182,14 +187,13 @@ def _step(p, t, nd):
     return p.select(-nd - 1, t if p.shape[-nd - 1] > 1 else 0)
 
 
-def _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=None):
-    """The sequential filter in plain torch ops: parameters broadcastable to [..., T | 1, ...] (m0, P0 without the
-    time axis), x [..., T, obs] -> (log_prob [...], filtered mean and covariance of the last state).  The same
-    arithmetic as csrc/gaussian_hmm.hip: P^p symmetrised, S = L L^T, U = P^p H L^-T, P = P^p - U U^T.  A step
-    whose S is not positive definite makes the element NaN.  ``keep``: a list that receives every step's (m_t, P_t)."""
-    T, o = x.shape[-2:]
+def _kalman_steps(m0, P0, F, q, Q, H, r, R, x):
+    """The sequential filter in plain torch ops, step by step: parameters broadcastable to [..., T | 1, ...] (m0, P0
+    without the time axis), x [..., T, obs]; yields per step (|L^-1 y|^2, sum log diag L, m_t, P_t, whether S had a
+    non-positive pivot).  The same arithmetic as csrc/gaussian_hmm.h: P^p symmetrised, S = L L^T, U = P^p H L^-T,
+    P = P^p - U U^T."""
+    T = x.shape[-2]
     m, P = m0, P0
-    lp, bad = 0.0, False
     for t in range(T):
         Ft, qt, Qt = _step(F, t, 2), _step(q, t, 1), _step(Q, t, 2)
         Ht, rt, Rt = _step(H, t, 2), _step(r, t, 1), _step(R, t, 2)
@@ -200,20 +204,47 @@ def _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=None):
         PH = Pp @ Ht
         S = Ht.transpose(-1, -2) @ PH + Rt
         L, info = torch.linalg.cholesky_ex(S)
-        bad = (info > 0) | bad
         batch = torch.broadcast_shapes(L.shape[:-2], y.shape[:-1], PH.shape[:-2])
         L = L.expand(batch + L.shape[-2:])
         v = torch.linalg.solve_triangular(L, y.expand(batch + y.shape[-1:]).unsqueeze(-1), upper=False)
         U = torch.linalg.solve_triangular(L, PH.expand(batch + PH.shape[-2:]).transpose(-1, -2),
                                           upper=False).transpose(-1, -2)
-        lp = lp - 0.5 * v.squeeze(-1).pow(2).sum(-1) - L.diagonal(dim1=-2, dim2=-1).log().sum(-1) \
-            - 0.5 * o * math.log(2 * math.pi)
         m = mp + (U @ v).squeeze(-1)
         P = Pp - U @ U.transpose(-1, -2)
+        yield v.squeeze(-1).pow(2).sum(-1), L.diagonal(dim1=-2, dim2=-1).log().sum(-1), m, P, info > 0
+
+
+def _kalman_filter(m0, P0, F, q, Q, H, r, R, x, keep=None):
+    """_kalman_steps -> (log_prob [...], filtered mean and covariance of the last state).  A step whose S is not
+    positive definite makes the element NaN.  ``keep``: a list that receives every step's (m_t, P_t)."""
+    o = x.shape[-1]
+    lp, bad = 0.0, False
+    for quad, logdet, m, P, info in _kalman_steps(m0, P0, F, q, Q, H, r, R, x):
+        bad = info | bad
+        lp = lp - 0.5 * quad - logdet - 0.5 * o * math.log(2 * math.pi)
         if keep is not None:
             keep.append((m, P))
     nan = lp.new_full((), float("nan"))
     return torch.where(bad, nan, lp), m, P
+
+
+def _kalman_terms(m0, P0, F, q, Q, H, r, R, x):
+    """_kalman_steps -> (quad = sum_t |L_t^-1 y_t|^2, logdet = sum_t sum log diag L_t, filtered mean and covariance
+    of the last state): the two halves of the Gaussian log_prob kept apart, what GammaGaussianHMM needs of the filter
+    at unit scale.  NaN (quad and logdet) where a step's S is not positive definite."""
+    quad, logdet, bad = 0.0, 0.0, False
+    for v2, ld, m, P, info in _kalman_steps(m0, P0, F, q, Q, H, r, R, x):
+        bad = info | bad
+        quad, logdet = quad + v2, logdet + ld
+    nan = quad.new_full((), float("nan"))
+    return torch.where(bad, nan, quad), torch.where(bad, nan, logdet), m, P
+
+
+def _student_log_prob(a, b, quad, logdet, n):
+    """log p(x) of the series when every covariance of the model is divided by s ~ Gamma(a, b): the unit-scale
+    filter's ``quad`` and ``logdet`` over n = T * obs_dim observed numbers, s integrated out."""
+    return (torch.lgamma(a + 0.5 * n) - torch.lgamma(a) + a * b.log() - (a + 0.5 * n) * (b + 0.5 * quad).log()
+            - logdet - 0.5 * n * math.log(2 * math.pi))
 
 
 def _backward_sample_maps(m0, P0, F, q, Q, H, r, R, x):
@@ -348,8 +379,8 @@ class GaussianHMM(TorchDistribution):
     again two launches (csrc/gaussian_hmm_draw.hip) for the same tensors when nothing needs a gradient, after the
     filter's one launch for a forecast; the generative loop in torch ops, reparameterised, otherwise.
 
-    Not built here: ``conjugate_update``, ``GammaGaussianHMM``, ``LinearHMM``, ``IndependentHMM``, ``GaussianMRF``
-    and the HMM reparametrisers."""
+    Not built here: ``conjugate_update``, ``LinearHMM``, ``IndependentHMM``, ``GaussianMRF`` and the HMM
+    reparametrisers."""
     arg_constraints = {}
     has_rsample = True
     support = constraints.independent(constraints.real, 2)
@@ -624,3 +655,110 @@ class GaussianHMM(TorchDistribution):
             xs.append((z.unsqueeze(-2) @ _step(H, t, 2)).squeeze(-2)
                       + draw(_step(r, t, 1), _step(R, t, 2), None if ex is None else ex[..., t, :]))
         return torch.stack(xs, dim=-2)
+
+
+# ---- GammaGaussianHMM --------------------------------------------------------------------------------------------
+class GammaGaussianHMM(TorchDistribution):
+    """Linear state-space model whose initial, process and observation noise share one Gamma-distributed precision
+    multiplier, so that the series is jointly multivariate Student-t (reference: pyro/distributions/hmm.py:744-940):
+
+        s = scale_dist.sample()
+        z = N(initial_dist.loc, initial_dist.covariance / s).sample()
+        for t in range(num_steps):
+            z = z @ transition_matrix + N(transition_dist.loc, transition_dist.covariance / s).sample()
+            x[t] = z @ observation_matrix + N(observation_dist.loc, observation_dist.covariance / s).sample()
+
+    Argument order and shape rules are the reference's: ``scale_dist`` is a ``Gamma`` (this package's or torch's)
+    whose batch shape joins the broadcast of the others', which are those of ``GaussianHMM``; each of the three noise
+    distributions is a ``MultivariateNormal`` or an ``Independent(Normal, 1)`` (the reference takes the former only).
+
+    The means, gains and covariance ratios of the Kalman filter do not depend on ``s``, so ONE filter at unit scale
+    gives ``quad = sum_t |L_t^-1 y_t|^2`` and ``logdet = sum_t sum log diag L_t`` and, with ``n = T * obs_dim``,
+
+        log_prob = lgamma(a + n/2) - lgamma(a) + a log b - (a + n/2) log(b + quad/2) - logdet - n/2 log(2 pi)
+
+    ``log_prob`` is differentiable in every parameter, in ``concentration`` and ``rate`` and in the value.  Device
+    tensors in float32 / float64 with hidden and obs dimension up to 16 take ONE launch of the Student-t variant of
+    the Kalman filter kernel (pa_gamma_gaussian_hmm_fwd_bwd: the filter, then the adjoint sweep of the Gaussian
+    model at covariances divided by ``w = (a + n/2) / (b + quad/2)``); everything else (CPU tensors, larger
+    dimensions, other dtypes, ``hmm.FUSED_GAUSSIAN_HMM = False``) the sequential torch filter of this module.
+
+    ``filter`` gives the posteriors of the multiplier and, at unit scale, of the final state.
+
+    Not built: ``rsample``, and ``smooth`` / ``rsample_posterior`` for this model."""
+    arg_constraints = {}
+    has_rsample = False
+    support = constraints.independent(constraints.real, 2)
+
+    def __init__(self, scale_dist, initial_dist, transition_matrix, transition_dist, observation_matrix,
+                 observation_dist, validate_args=None, duration=None):
+        if not isinstance(scale_dist, torch.distributions.Gamma):
+            raise ValueError("scale_dist must be a Gamma, got {}".format(type(scale_dist).__name__))
+        unit = GaussianHMM(initial_dist, transition_matrix, transition_dist, observation_matrix, observation_dist,
+                           validate_args=False, duration=duration)
+        batch_shape = torch.Size(torch.broadcast_shapes(scale_dist.batch_shape, unit.batch_shape))
+        self._setup(scale_dist.concentration, scale_dist.rate, unit, batch_shape, validate_args)
+
+    def _setup(self, concentration, rate, unit, batch_shape, validate_args):
+        # (the unit-scale model carries the whole batch shape: its expand touches the initial state alone)
+        self._unit = unit if unit.batch_shape == batch_shape else unit.expand(batch_shape)
+        self.concentration, self.rate = concentration, rate
+        self.hidden_dim, self.obs_dim, self.duration = unit.hidden_dim, unit.obs_dim, unit.duration
+        super().__init__(batch_shape, unit.event_shape, validate_args=validate_args)
+
+    def expand(self, batch_shape, _instance=None):
+        new = self._get_checked_instance(GammaGaussianHMM, _instance)
+        batch_shape = torch.Size(torch.broadcast_shapes(self.batch_shape, tuple(batch_shape)))
+        new._setup(self.concentration, self.rate, self._unit, batch_shape, False)
+        new._validate_args = self.__dict__.get("_validate_args")
+        return new
+
+    def _validate_sample(self, value):
+        pass        # time may be longer than event_shape[0] for time-homogeneous parameters
+
+    def _takes_kernel(self, value):
+        from .. import kernels
+        return (self._unit._takes_kernel(value)
+                and all(kernels.on_device(t) and t.dtype == value.dtype for t in (self.concentration, self.rate)))
+
+    def _kernel_scale(self, batch):
+        """``concentration`` and ``rate`` as kernels.gamma_gaussian_hmm_fwd_bwd takes them: [1] when shared by the
+        series (batch stride 0), else [B]."""
+        out = []
+        for p in (self.concentration, self.rate):
+            out.append(p.reshape(1) if p.numel() == 1 else p.expand(batch).reshape(-1).contiguous())
+        return out
+
+    def log_prob(self, value):
+        batch, T = self._unit._check_value(value)
+        if self._takes_kernel(value):
+            from ..ops.contract import _GammaGaussianHMM
+            return _GammaGaussianHMM.invoke(*self._kernel_scale(batch),
+                                            *self._unit._kernel_inputs(value, batch, T)).reshape(batch)
+        quad, logdet, _, _ = _kalman_terms(*self._unit._parts, value)
+        return _student_log_prob(self.concentration, self.rate, quad, logdet, T * self.obs_dim).expand(batch)
+
+    def filter(self, value):
+        """The posteriors given the observations ``value``: ``(Gamma, MultivariateNormal)`` of batch shape
+        ``batch_shape`` -- the multiplier's, ``Gamma(a + n/2, b + quad/2)``, and the final state's at unit scale (given
+        ``s`` its covariance is the returned one divided by ``s``).  The normal has the filter's ``m_T`` as location
+        and the filter's ``P_T`` as COVARIANCE.  (The reference builds its normal with ``scale_tril =
+        cholesky(precision)``, so that its ``scale_tril scale_tril^T`` is ``P_T^-1``.)  From the forward pass alone and
+        DETACHED from the parameters, as ``GaussianHMM.filter`` is."""
+        from . import Gamma, MultivariateNormal
+        batch, T = self._unit._check_value(value)
+        n = T * self.obs_dim
+        with torch.no_grad():
+            if self._takes_kernel(value):
+                from .. import kernels
+                args = [t.detach() for t in self._kernel_scale(batch) + self._unit._kernel_inputs(value, batch, T)]
+                quad, _, (m, P), _ = kernels.gamma_gaussian_hmm_fwd_bwd(*args, need_grads=False, need_filter=True)
+                quad, m, P = quad.reshape(batch), m.reshape(batch + m.shape[-1:]), P.reshape(batch + P.shape[-2:])
+            else:
+                quad, _, m, P = _kalman_terms(*self._unit._parts, value)
+                m, P = m.expand(batch + m.shape[-1:]), P.expand(batch + P.shape[-2:])
+                P = 0.5 * (P + P.transpose(-1, -2))
+            a = (self.concentration + 0.5 * n).expand(batch)
+            b = (self.rate + 0.5 * quad).expand(batch)
+        return (Gamma(a, b, validate_args=self._validate_args),
+                MultivariateNormal(m, covariance_matrix=P, validate_args=self._validate_args))

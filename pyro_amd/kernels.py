@@ -903,6 +903,44 @@ def gaussian_hmm_fwd_bwd(m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filt
     return log_prob, filt, grads
 
 
+def gamma_gaussian_hmm_fwd_bwd(concentration, rate, m0, P0, F, q, Q, H, r, R, x, need_grads=True, need_filter=False):
+    """That model with every covariance divided by one s ~ Gamma(concentration, rate) per sequence -- a jointly
+    Student-t series -- filtered at unit scale and differentiated in ONE launch (pa_gamma_gaussian_hmm_fwd_bwd).
+    ``concentration`` and ``rate``: [B | 1] of x's dtype; the other arguments in the layouts of gaussian_hmm_fwd_bwd.
+    -> (quad [B], logdet [B], filt, grads): quad = sum_t |L_t^-1 y_t|^2 and logdet = sum_t sum log diag L_t, from
+    which, with n = T * obs,
+
+        log_prob = lgamma(a + n/2) - lgamma(a) + a log b - (a + n/2) log(b + quad/2) - logdet - n/2 log(2 pi)
+
+    ``filt`` and ``grads`` (the nine gradients of that log_prob[b] with respect to m0 .. x) as for
+    gaussian_hmm_fwd_bwd; the gradients with respect to concentration and rate are closed forms of quad, the
+    caller's.  A sequence with a non-positive pivot gets NaN."""
+    params = (m0, P0, F, q, Q, H, r, R)
+    B, T, h, o, strides, steps = _gaussian_hmm_layout(params, x)
+    _require_gpu(concentration, rate)
+    for p in (concentration, rate):
+        assert p.dtype == x.dtype and p.dim() == 1 and p.shape[0] in (1, B) and p.is_contiguous(), \
+            "gamma_gaussian_hmm: concentration and rate [B | 1] contiguous of x's dtype"
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, dtype=x.dtype, device=x.device)     # noqa: E731
+    quad, logdet = new(B), new(B)
+    filt = (new(B, h), new(B, h, h)) if need_filter else None
+    grads = None
+    if need_grads:
+        grads = (new(B, h), new(B, h, h), new(B, steps[0], h, h), new(B, steps[1], h), new(B, steps[2], h, h),
+                 new(B, steps[3], h, o), new(B, steps[4], o), new(B, steps[5], o, o), new(B, T, o))
+    nbytes = lib.pa_gaussian_hmm_workspace(_dtype(x), B, T, h, o, int(need_grads))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    args = _gaussian_hmm_args(params, x, strides, B, T, h, o)
+    args[1:1] = [_ptr(concentration), int(concentration.shape[0] != 1), _ptr(rate), int(rate.shape[0] != 1)]
+    args += [_ptr(quad), _ptr(logdet)]
+    args += [_ptr(t) for t in (filt or (None, None))]
+    args += [_ptr(g) for g in (grads or (None,) * 9)]
+    args += [_ptr(ws), nbytes, _stream()]
+    check(lib.pa_gamma_gaussian_hmm_fwd_bwd(*args))
+    return quad, logdet, filt, grads
+
+
 def gaussian_hmm_sample(m0, P0, F, q, Q, H, r, R, x, eps, need_maps=False):
     """Draws of the latent path z_1..z_T of that model given the data x, forward filter and backward sample in two
     launches (pa_gaussian_hmm_sample).  Parameters and x in the layouts of gaussian_hmm_fwd_bwd; ``eps`` [S, B, T, h]

@@ -531,6 +531,42 @@ class _GaussianHMM(torch.autograd.Function):
         return tuple(out)
 
 
+@_dispatcher_op("gamma_gaussian_hmm")
+class _GammaGaussianHMM(torch.autograd.Function):
+    """log p(x) of that model with every covariance divided by one s ~ Gamma(a, b) per sequence (a jointly Student-t
+    series): the filter at unit scale and the adjoint sweep at covariances divided by w = (a + n/2) / (b + quad/2),
+    ONE launch (pa_gamma_gaussian_hmm_fwd_bwd).  Arguments in the layouts of kernels.gamma_gaussian_hmm_fwd_bwd."""
+
+    @staticmethod
+    def forward(ctx, a, b, m0, P0, F, q, Q, H, r, R, x):
+        need = any(ctx.needs_input_grad[2:])
+        quad, logdet, _, grads = kernels.gamma_gaussian_hmm_fwd_bwd(a, b, m0, P0, F, q, Q, H, r, R, x,
+                                                                    need_grads=need)
+        n = x.shape[1] * x.shape[2]
+        ctx.save_for_backward(a, b, quad, *(grads or ()))
+        ctx.n = n
+        ctx.shapes = tuple(t.shape for t in (a, b, m0, P0, F, q, Q, H, r, R, x))
+        from ..distributions.hmm import _student_log_prob
+        return _student_log_prob(a, b, quad, logdet, n)
+
+    @staticmethod
+    def backward(ctx, g):
+        from ..distributions.fused import _sum_to
+        a, b, quad, *grads = ctx.saved_tensors
+        an, bq = a + 0.5 * ctx.n, b + 0.5 * quad
+        # the closed forms for the Gamma's two parameters, then the kernel's nine
+        grads = [torch.digamma(an) - torch.digamma(a) + b.log() - bq.log(), a / b - an / bq] + (grads or [None] * 9)
+        out = []
+        for grad, shape, needed in zip(grads, ctx.shapes, ctx.needs_input_grad):
+            if not needed:
+                out.append(None)
+                continue
+            d = g.reshape((-1,) + (1,) * (grad.dim() - 1)) * grad
+            # a parameter shared by the sequences: the sum over them is ours (the steps were summed in the kernel)
+            out.append(_sum_to(d, d.new_empty(shape)) if d.shape != shape else d)
+        return tuple(out)
+
+
 def _match_chain(terms, sum_ids, ready=None):
     """The pattern of the chain kernels: a component whose names form a simple path (every term mentions one or two
     of them, the two-name terms link consecutive variables: an HMM written with pyro.markov), at most 64 states, one

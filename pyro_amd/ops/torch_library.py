@@ -136,6 +136,18 @@ def _register():
                      x.new_empty((B, steps[4], o)), x.new_empty((B, steps[5], o, o)), x.new_empty((B, T, o))]
         return x.new_empty((B,)), x.new_empty((B, h)), x.new_empty((B, h, h)), grads
 
+    @lib.register_fake("pyro_amd::gamma_gaussian_hmm")
+    def _(concentration, rate, m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, x, need_grads):
+        B, T, o = x.shape
+        h = m0.shape[-1]
+        grads = []
+        if need_grads:
+            steps = [t.shape[1] for t in (trans, trans_loc, trans_cov, obs, obs_loc, obs_cov)]
+            grads = [x.new_empty((B, h)), x.new_empty((B, h, h)), x.new_empty((B, steps[0], h, h)),
+                     x.new_empty((B, steps[1], h)), x.new_empty((B, steps[2], h, h)), x.new_empty((B, steps[3], h, o)),
+                     x.new_empty((B, steps[4], o)), x.new_empty((B, steps[5], o, o)), x.new_empty((B, T, o))]
+        return x.new_empty((B,)), x.new_empty((B,)), x.new_empty((B, h)), x.new_empty((B, h, h)), grads
+
     @lib.register_fake("pyro_amd::gaussian_hmm_sample")
     def _(m0, P0, trans, trans_loc, trans_cov, obs, obs_loc, obs_cov, x, eps, need_maps):
         B, T, _o = x.shape
@@ -638,4 +650,4 @@ def registered_ops():
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
              "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw",
-             "gaussian_hmm_smooth")
+             "gaussian_hmm_smooth", "gamma_gaussian_hmm")
