@@ -1037,6 +1037,24 @@ int pa_gaussian_hmm_draw(int dtype, const void* m0, int64_t m0_stride_batch, con
                          int64_t obs, int64_t S, const void* eps0, const void* eps_z, const void* eps_x, void* x,
                          void* z, void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/linear_hmm.hip: forward draws of a linear state-space model with arbitrary noise -----------------------
+ * Replaces LinearHMM.rsample (pyro/distributions/hmm.py:1122-1138 over _linear_integrate, hmm.py:32-48: a Python
+ * loop over T of one batched matmul, then the observation map) with ONE launch on the caller's stream.
+ *   z_0 = init,   z_t = z_{t-1} F_t + e_t,   y_t = z_t H_t + n_t,   t = 1..T
+ * in the row-vector conventions above: F multiplies init at the first step already.  init [S, B, hidden],
+ * e [S, B, T, hidden], n [S, B, T, obs] are draws of the initial, transition and observation noise with their
+ * locations and scales applied (NOT standard normals), contiguous; F [B | 1, T | 1, hidden, hidden] and
+ * H [B | 1, T | 1, hidden, obs] with a batch stride and a step stride in elements (0 = shared by the sequences,
+ * respectively time-homogeneous).  One lane per draw writes y[s, b, t, :] and, when z is not NULL, z[s, b, t, :];
+ * y [S, B, T, obs], z [S, B, T, hidden] contiguous.  z_0 is not written.
+ * No workspace, no atomics: bit-reproducible, and a draw depends neither on S nor on the other sequences.
+ * Non-finite noise flows into that draw's outputs and nowhere else.  hidden or obs > 16: PA_ERR_UNSUPPORTED.
+ * B = 0 or S = 0: PA_OK without a launch. */
+int pa_linear_hmm_draw(int dtype, const void* F, int64_t F_stride_batch, int64_t F_stride_step, const void* H,
+                       int64_t H_stride_batch, int64_t H_stride_step, int64_t B, int64_t T, int64_t hidden,
+                       int64_t obs, int64_t S, const void* init, const void* e, const void* n, void* y, void* z,
+                       pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -351,6 +351,9 @@ _SIGNATURES = {
                              + [c_int64] * 5 + [c_void_p] * 3                                     # B T hidden obs S, noise
                              + [c_void_p, c_void_p]                                               # x, z
                              + [c_void_p, c_size_t, c_void_p]),
+    "pa_linear_hmm_draw": (c_int, [c_int] + [c_void_p, c_int64, c_int64] * 2                      # F H
+                           + [c_int64] * 5 + [c_void_p] * 3                                       # B T hidden obs S, noise
+                           + [c_void_p, c_void_p, c_void_p]),                                     # y, z, stream
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -595,6 +595,46 @@ std::tuple<at::Tensor, std::vector<at::Tensor>> gaussian_hmm_draw(
   return {x, states};
 }
 
+// forward draws of a linear state-space model with arbitrary noise in one launch (pyro/distributions/hmm.py:1122-1138
+// LinearHMM.rsample over _linear_integrate, hmm.py:32-48).  Layouts as kernels.linear_hmm_draw: trans
+// [B | 1, T | 1, h, h], obs [B | 1, T | 1, h, o], T steps, the noise draws init [S, B, h], e [S, B, T, h], n [S, B, T, o]
+// with loc and scale applied -> y [S, B, T, o] and, with need_states, [z [S, B, T, h]] (empty without)
+std::tuple<at::Tensor, std::vector<at::Tensor>> linear_hmm_draw(const at::Tensor& trans, const at::Tensor& obs,
+                                                                int64_t T, const at::Tensor& init, const at::Tensor& e,
+                                                                const at::Tensor& n, bool need_states) {
+  const int dt = dtype_of(init, "linear_hmm_draw");
+  TORCH_CHECK(init.dim() == 3 && init.is_contiguous() && obs.dim() == 4 && trans.dim() == 4 && T >= 1,
+              "pyro_amd::linear_hmm_draw: init [S, B, hidden] contiguous, trans [B | 1, T | 1, hidden, hidden], "
+              "obs [B | 1, T | 1, hidden, obs], T >= 1");
+  const int64_t S = init.size(0), B = init.size(1), h = init.size(2), o = obs.size(3);
+  auto matrix_ok = [&](const at::Tensor& m, int64_t cols) {
+    return m.is_cuda() && m.scalar_type() == init.scalar_type() && m.is_contiguous() &&
+           (m.size(0) == 1 || m.size(0) == B) && (m.size(1) == 1 || m.size(1) == T) && m.size(2) == h &&
+           m.size(3) == cols;
+  };
+  TORCH_CHECK(h >= 1 && o >= 1 && matrix_ok(trans, h) && matrix_ok(obs, o),
+              "pyro_amd::linear_hmm_draw: trans [B | 1, T | 1, hidden, hidden], obs [B | 1, T | 1, hidden, obs] "
+              "contiguous of the noise's dtype");
+  auto noise_ok = [&](const at::Tensor& t, int64_t w) {
+    return t.is_cuda() && t.scalar_type() == init.scalar_type() && t.is_contiguous() && t.dim() == 4 &&
+           t.size(0) == S && t.size(1) == B && t.size(2) == T && t.size(3) == w;
+  };
+  TORCH_CHECK(noise_ok(e, h) && noise_ok(n, o),
+              "pyro_amd::linear_hmm_draw: e [S, B, T, hidden], n [S, B, T, obs] contiguous of init's dtype");
+  auto stride_batch = [&](const at::Tensor& m) { return m.size(0) == 1 ? 0 : m.size(1) * m.size(2) * m.size(3); };
+  auto stride_step = [&](const at::Tensor& m) { return m.size(1) == 1 ? 0 : m.size(2) * m.size(3); };
+  const auto opt = init.options();
+  at::Tensor y = at::empty({S, B, T, o}, opt);
+  std::vector<at::Tensor> states;
+  if (need_states) states = {at::empty({S, B, T, h}, opt)};
+  check(pa_linear_hmm_draw(dt, trans.data_ptr(), stride_batch(trans), stride_step(trans), obs.data_ptr(),
+                           stride_batch(obs), stride_step(obs), B, T, h, o, S, init.data_ptr(), e.data_ptr(),
+                           n.data_ptr(), y.data_ptr(), need_states ? states[0].data_ptr() : nullptr,
+                           current_stream()),
+        "linear_hmm_draw");
+  return {y, states};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -782,6 +822,8 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("gaussian_hmm_draw(Tensor m0, Tensor P0, Tensor trans, Tensor trans_loc, Tensor trans_cov, Tensor obs, "
         "Tensor obs_loc, Tensor obs_cov, int T, Tensor eps0, Tensor eps_z, Tensor eps_x, bool need_states) -> "
         "(Tensor x, Tensor[] states)");
+  m.def("linear_hmm_draw(Tensor trans, Tensor obs, int T, Tensor init, Tensor e, Tensor n, bool need_states) -> "
+        "(Tensor y, Tensor[] states)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -815,6 +857,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("gaussian_hmm_sample", &gaussian_hmm_sample);
   m.impl("gaussian_hmm_smooth", &gaussian_hmm_smooth);
   m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);
+  m.impl("linear_hmm_draw", &linear_hmm_draw);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

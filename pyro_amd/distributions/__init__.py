@@ -125,5 +125,5 @@ class Independent(torch.distributions.Independent, TorchDistributionMixin):
     def fused_score_term(self, value, scale=1.0, mask=None):
         f = getattr(self.base_dist, "fused_score_term", None) if mask is None else None
         return None if f is None else f(value, scale, mask)
-from .hmm import DiscreteHMM, GammaGaussianHMM, GaussianHMM  # noqa: E402,F401
-__all__ += ["DiscreteHMM", "GammaGaussianHMM", "GaussianHMM"]
+from .hmm import DiscreteHMM, GammaGaussianHMM, GaussianHMM, IndependentHMM, LinearHMM  # noqa: E402,F401
+__all__ += ["DiscreteHMM", "GammaGaussianHMM", "GaussianHMM", "IndependentHMM", "LinearHMM"]

@@ -25,6 +25,12 @@ GammaGaussianHMM: that model with one Gamma-distributed precision multiplier sha
 Student-t series (reference: pyro/distributions/hmm.py:744-940).  log_prob is ONE launch of the Student-t variant of
 the same kernel (pa_gamma_gaussian_hmm_fwd_bwd): the filter at unit scale, then the adjoint sweep at covariances
 divided by the series' weight; the routing and the torch route are GaussianHMM's.
+
+LinearHMM: the same linear model with arbitrary reparameterisable noise and optional observation transforms
+(reference: pyro/distributions/hmm.py:939-1138).  It has no log_prob; rsample is the reference's Python loop over T
+of small batched matmuls (_linear_integrate, hmm.py:32-48), here ONE launch with one lane per sample path
+(pa_linear_hmm_draw) when nothing needs a gradient, and that loop in torch ops otherwise.  IndependentHMM: the
+reference's wrapper that reads a batch of univariate HMMs as one multivariate one (hmm.py:1141-1198).
 """
 import math
 
@@ -379,8 +385,10 @@ class GaussianHMM(TorchDistribution):
     again two launches (csrc/gaussian_hmm_draw.hip) for the same tensors when nothing needs a gradient, after the
     filter's one launch for a forecast; the generative loop in torch ops, reparameterised, otherwise.
 
-    Not built here: ``conjugate_update``, ``LinearHMM``, ``IndependentHMM``, ``GaussianMRF`` and the HMM
-    reparametrisers."""
+    ``LinearHMM`` (arbitrary noise, no ``log_prob``) and ``IndependentHMM`` are below; ``infer.reparam`` has
+    ``LinearHMMReparam`` and ``StudentTReparam``, which turn a heavy-tailed ``LinearHMM`` site into this class with
+    per-step diagonal covariances.  Not built here: ``conjugate_update``, ``GaussianMRF``, ``Stable`` and its
+    reparameterisers, and missing observations."""
     arg_constraints = {}
     has_rsample = True
     support = constraints.independent(constraints.real, 2)
@@ -762,3 +770,243 @@ class GammaGaussianHMM(TorchDistribution):
             b = (self.rate + 0.5 * quad).expand(batch)
         return (Gamma(a, b, validate_args=self._validate_args),
                 MultivariateNormal(m, covariance_matrix=P, validate_args=self._validate_args))
+
+
+# ---- LinearHMM ---------------------------------------------------------------------------------------------------
+FUSED_LINEAR_HMM = True       # device tensors within the kernel's limits go through pa_linear_hmm_draw
+
+
+def _kernel_matrix(m, nb):
+    """A matrix [batch..., T | 1, rows, cols] as kernels.linear_hmm_draw takes it, [B | 1, T | 1, rows, cols]
+    contiguous: the eager expansion is undone where it was one (stride 0), so that a shared matrix stays shared and a
+    time-homogeneous one is staged once."""
+    if all(m.shape[i] == 1 or m.stride(i) == 0 for i in range(nb)):
+        m = m[(0,) * nb].unsqueeze(0)
+    else:
+        m = m.reshape((-1,) + tuple(m.shape[nb:]))
+    if m.shape[1] > 1 and m.stride(1) == 0:
+        m = m[:, :1]
+    return m.contiguous()
+
+
+class LinearHMM(TorchDistribution):
+    """Hidden Markov model with linear dynamics and observations and ARBITRARY reparameterisable noise for the
+    initial, transition and observation distributions (reference: pyro/distributions/hmm.py:939-1138), the
+    generative model
+
+        z = initial_dist.sample()
+        for t in range(num_steps):
+            z = z @ transition_matrix + transition_dist.sample()
+            y = z @ observation_matrix + obs_base_dist.sample()
+            x[t] = obs_transform(y)
+
+    where ``observation_dist`` is split into ``obs_base_dist`` and the transforms peeled off its
+    ``TransformedDistribution`` layers.  ``event_shape = (num_steps, obs_dim)``; argument checks and shape rules are
+    the reference's: the time axis comes from broadcasting, ``duration`` names it for time-homogeneous parameters,
+    everything is expanded eagerly.
+
+    There is no ``log_prob``: train through ``infer.reparam.LinearHMMReparam``, which makes the site a conditionally
+    Gaussian ``GaussianHMM``.
+
+    ``rsample`` is ONE launch (csrc/linear_hmm.hip) for device tensors when nothing needs a gradient, the loop in
+    torch ops, reparameterised, otherwise."""
+    arg_constraints = {}
+    has_rsample = True
+
+    def __init__(self, initial_dist, transition_matrix, transition_dist, observation_matrix, observation_dist,
+                 validate_args=None, duration=None):
+        if not isinstance(transition_matrix, torch.Tensor) or transition_matrix.dim() < 2:
+            raise ValueError("transition_matrix must be a tensor [..., hidden_dim, hidden_dim]")
+        if not isinstance(observation_matrix, torch.Tensor) or observation_matrix.dim() < 2:
+            raise ValueError("observation_matrix must be a tensor [..., hidden_dim, obs_dim]")
+        for d, what in ((initial_dist, "initial_dist"), (transition_dist, "transition_dist"),
+                        (observation_dist, "observation_dist")):
+            if not d.has_rsample or len(d.event_shape) != 1:
+                raise ValueError("{} must be reparameterisable with one event dim".format(what))
+        hidden_dim, obs_dim = observation_matrix.shape[-2:]
+        if initial_dist.event_shape != (hidden_dim,) or transition_dist.event_shape != (hidden_dim,) \
+                or transition_matrix.shape[-2:] != (hidden_dim, hidden_dim) \
+                or observation_dist.event_shape != (obs_dim,):
+            raise ValueError("expected initial_dist and transition_dist over {0} dims, transition_matrix "
+                             "[..., {0}, {0}] and observation_dist over {1} dims".format(hidden_dim, obs_dim))
+        shape = torch.broadcast_shapes(initial_dist.batch_shape + (1,), transition_matrix.shape[:-2],
+                                       transition_dist.batch_shape, observation_matrix.shape[:-2],
+                                       observation_dist.batch_shape)
+        batch_shape, time_shape = torch.Size(shape[:-1]), torch.Size(shape[-1:])
+        event_shape = self._init_duration(duration, time_shape + (obs_dim,))
+        super().__init__(batch_shape, event_shape, validate_args=validate_args)
+
+        # expand eagerly
+        if initial_dist.batch_shape != batch_shape:
+            initial_dist = initial_dist.expand(batch_shape)
+        if transition_matrix.shape[:-2] != batch_shape + time_shape:
+            transition_matrix = transition_matrix.expand(batch_shape + time_shape + (hidden_dim, hidden_dim))
+        if transition_dist.batch_shape != batch_shape + time_shape:
+            transition_dist = transition_dist.expand(batch_shape + time_shape)
+        if observation_matrix.shape[:-2] != batch_shape + time_shape:
+            observation_matrix = observation_matrix.expand(batch_shape + time_shape + (hidden_dim, obs_dim))
+        if observation_dist.batch_shape != batch_shape + time_shape:
+            observation_dist = observation_dist.expand(batch_shape + time_shape)
+
+        # the observation transforms
+        transforms = []
+        while True:
+            if isinstance(observation_dist, torch.distributions.Independent):
+                observation_dist = observation_dist.base_dist
+            elif isinstance(observation_dist, torch.distributions.TransformedDistribution):
+                transforms = list(observation_dist.transforms) + transforms
+                observation_dist = observation_dist.base_dist
+            else:
+                break
+        if not observation_dist.event_shape:
+            from . import Independent
+            observation_dist = Independent(observation_dist, 1)
+
+        self.hidden_dim, self.obs_dim = hidden_dim, obs_dim
+        self.initial_dist = initial_dist
+        self.transition_matrix = transition_matrix
+        self.transition_dist = transition_dist
+        self.observation_matrix = observation_matrix
+        self.observation_dist = observation_dist
+        self.transforms = transforms
+
+    def _init_duration(self, duration, event_shape):
+        """The reference's duration rule (hmm.py:200-215) -> the event shape, its time axis named by ``duration``."""
+        if duration is None:
+            if event_shape[0] != 1:
+                duration = event_shape[0]
+        elif duration != event_shape[0]:
+            if event_shape[0] != 1:
+                raise ValueError("duration, event_shape mismatch: {} vs {}".format(duration, event_shape))
+            event_shape = (duration,) + tuple(event_shape[1:])
+        self.duration = duration
+        return torch.Size(event_shape)
+
+    @constraints.dependent_property(event_dim=2)
+    def support(self):
+        return constraints.independent(self.observation_dist.support, 1)
+
+    def expand(self, batch_shape, _instance=None):
+        new = self._get_checked_instance(LinearHMM, _instance)
+        batch_shape = torch.Size(batch_shape)
+        time_shape = self.transition_dist.batch_shape[-1:]
+        h, o = self.hidden_dim, self.obs_dim
+        new.hidden_dim, new.obs_dim, new.duration = h, o, self.duration
+        new.initial_dist = self.initial_dist.expand(batch_shape)
+        new.transition_matrix = self.transition_matrix.expand(batch_shape + time_shape + (h, h))
+        new.transition_dist = self.transition_dist.expand(batch_shape + time_shape)
+        new.observation_matrix = self.observation_matrix.expand(batch_shape + time_shape + (h, o))
+        new.observation_dist = self.observation_dist.expand(batch_shape + time_shape)
+        new.transforms = self.transforms
+        super(LinearHMM, new).__init__(batch_shape, self.event_shape, validate_args=False)
+        new._validate_args = self.__dict__.get("_validate_args")
+        return new
+
+    def log_prob(self, value):
+        raise NotImplementedError("LinearHMM.log_prob() is not implemented")
+
+    def rsample(self, sample_shape=torch.Size(), *, noise=None):
+        """Sample paths of the observations, ``sample_shape + batch_shape + (duration, obs_dim)`` (reference:
+        hmm.py:1122-1138); needs ``duration``.
+
+            z_0 = init,   z_t = z_{t-1} F_t + e_t,   x_t = transforms(z_t H_t + n_t)
+
+        ``noise``: the triple ``(init, e, n)`` of DRAWS of the three component distributions (location and scale
+        applied, not standard normals) of shapes ``sample_shape + batch_shape`` + ``(hidden_dim,)``,
+        ``(duration, hidden_dim)`` and ``(duration, obs_dim)``.  (The keyword is this package's, as for
+        ``GaussianHMM.rsample``.)  Not given, it is the three components' own ``rsample(sample_shape)`` in the
+        reference's order: initial, transition expanded to the duration, then observation.
+
+        Device tensors of one dtype, float32 or float64, with hidden and obs dimension up to 16 and nothing requiring
+        a gradient under grad mode take the ONE launch of csrc/linear_hmm.hip and the result is DETACHED.  Everything
+        else -- grad mode with a matrix or the noise (hence a component's parameter) requiring a gradient, CPU
+        tensors, larger dimensions, other or mixed dtypes, ``hmm.FUSED_LINEAR_HMM = False`` -- is the loop in torch
+        ops: reparameterised in the matrices and, through the components' ``rsample``, in their parameters.  The
+        transforms are applied by torch after either route."""
+        if self.duration is None:
+            raise ValueError("LinearHMM.rsample needs a duration (time-homogeneous parameters do not tell it)")
+        T, h, o = self.duration, self.hidden_dim, self.obs_dim
+        sample_shape = torch.Size(sample_shape)
+        shape = sample_shape + self.batch_shape
+        shapes = (shape + (h,), shape + (T, h), shape + (T, o))
+        if noise is None:
+            init = self.initial_dist.rsample(sample_shape)
+            e = self.transition_dist.expand(self.batch_shape + (T,)).rsample(sample_shape)
+            n = self.observation_dist.expand(self.batch_shape + (T,)).rsample(sample_shape)
+            noise = (init, e, n)
+        else:
+            noise = tuple(noise)
+            if len(noise) != 3 or any(e.shape != s for e, s in zip(noise, shapes)):
+                raise ValueError("expected noise as a triple of shapes {}, {} and {}, got {}".format(
+                    *(tuple(s) for s in shapes), [tuple(e.shape) for e in noise]))
+        F, H = self.transition_matrix, self.observation_matrix
+        tensors = (F, H) + noise
+        needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+        from .. import kernels
+        if (not needs_grad and FUSED_LINEAR_HMM and F.dtype in (torch.float32, torch.float64)
+                and all(kernels.on_device(t) and t.dtype == F.dtype for t in tensors)
+                and h <= kernels.GAUSSIAN_HMM_MAX_HIDDEN and o <= kernels.GAUSSIAN_HMM_MAX_OBS
+                and self.batch_shape.numel() > 0):
+            nb, B = len(self.batch_shape), self.batch_shape.numel()
+            mats = [_kernel_matrix(m.detach(), nb) for m in (F, H)]
+            draws = [t.detach().reshape((-1, B) + tuple(s[len(shape):])).contiguous() for t, s in zip(noise, shapes)]
+            x, _ = kernels.linear_hmm_draw(*mats, T, *draws)
+            x = x.reshape(shapes[2])
+        else:
+            z, (e, n) = noise[0], noise[1:]
+            xs = []
+            for t in range(T):
+                z = (z.unsqueeze(-2) @ _step(F, t, 2)).squeeze(-2) + e[..., t, :]
+                xs.append((z.unsqueeze(-2) @ _step(H, t, 2)).squeeze(-2) + n[..., t, :])
+            x = torch.stack(xs, dim=-2)
+        for t in self.transforms:
+            x = t(x)
+        return x
+
+
+class IndependentHMM(TorchDistribution):
+    """A batch of independent univariate HMMs seen as one multivariate distribution (reference:
+    pyro/distributions/hmm.py:1141-1198): ``base_dist`` with batch shape ``shape + (obs_dim,)`` and event shape
+    ``(duration, 1)`` becomes a distribution with batch shape ``shape`` and event shape ``(duration, obs_dim)``."""
+    arg_constraints = {}
+
+    def __init__(self, base_dist):
+        if not base_dist.batch_shape or len(base_dist.event_shape) != 2 or base_dist.event_shape[-1] != 1:
+            raise ValueError("expected a base HMM with at least one batch dim and event shape (duration, 1), got "
+                             "batch shape {} and event shape {}".format(tuple(base_dist.batch_shape),
+                                                                        tuple(base_dist.event_shape)))
+        batch_shape = base_dist.batch_shape[:-1]
+        event_shape = base_dist.event_shape[:-1] + base_dist.batch_shape[-1:]
+        super().__init__(batch_shape, event_shape)
+        self.base_dist = base_dist
+
+    @constraints.dependent_property(event_dim=2)
+    def support(self):
+        return self.base_dist.support
+
+    @property
+    def has_rsample(self):
+        return self.base_dist.has_rsample
+
+    @property
+    def duration(self):
+        return self.base_dist.duration
+
+    def expand(self, batch_shape, _instance=None):
+        batch_shape = torch.Size(batch_shape)
+        new = self._get_checked_instance(IndependentHMM, _instance)
+        new.base_dist = self.base_dist.expand(batch_shape + self.base_dist.batch_shape[-1:])
+        super(IndependentHMM, new).__init__(batch_shape, self.event_shape, validate_args=False)
+        new._validate_args = self.__dict__.get("_validate_args")
+        return new
+
+    def _validate_sample(self, value):
+        pass        # the base distribution checks what it is given
+
+    def rsample(self, sample_shape=torch.Size()):
+        base_value = self.base_dist.rsample(sample_shape)
+        return base_value.squeeze(-1).transpose(-1, -2)
+
+    def log_prob(self, value):
+        base_value = value.transpose(-1, -2).unsqueeze(-1)
+        return self.base_dist.log_prob(base_value).sum(-1)

@@ -1026,6 +1026,43 @@ def gaussian_hmm_draw(m0, P0, F, q, Q, H, r, R, T, eps0, eps_z, eps_x, need_stat
     return x, z
 
 
+def linear_hmm_draw(F, H, T, init, e, n, need_states=False):
+    """Forward draws of a linear state-space model with ARBITRARY noise in ONE launch (pa_linear_hmm_draw):
+    z_0 = init, z_t = z_{t-1} F_t + e_t, y_t = z_t H_t + n_t for t = 1..T (row vectors; F multiplies init at the
+    first step already).  ``F`` [B | 1, T | 1, h, h] and ``H`` [B | 1, T | 1, h, o] in the layouts of
+    gaussian_hmm_fwd_bwd; ``init`` [S, B, h], ``e`` [S, B, T, h], ``n`` [S, B, T, o] contiguous: draws of the initial,
+    transition and observation noise with loc and scale applied, not standard normals.  -> (y [S, B, T, o],
+    z [S, B, T, h] with ``need_states``, else None).  One lane per draw; a draw's bits depend neither on S nor on the
+    other sequences, and non-finite noise stays in its own draw.  Nothing here is differentiable.  hidden or obs over
+    GAUSSIAN_HMM_MAX_HIDDEN / GAUSSIAN_HMM_MAX_OBS raises Unsupported."""
+    _require_gpu(F, H, init, e, n)
+    assert init.dim() == 3 and F.dim() == 4 and H.dim() == 4, \
+        "linear_hmm_draw: init [S, B, hidden], F [B | 1, T | 1, hidden, hidden], H [B | 1, T | 1, hidden, obs]"
+    S, B, h = init.shape
+    o, T = H.shape[-1], int(T)
+    assert T >= 1 and h >= 1 and o >= 1
+    if h > GAUSSIAN_HMM_MAX_HIDDEN or o > GAUSSIAN_HMM_MAX_OBS:
+        raise Unsupported("pyro_amd: linear_hmm_draw: hidden=%d obs=%d over the limit of %d / %d"
+                          % (h, o, GAUSSIAN_HMM_MAX_HIDDEN, GAUSSIAN_HMM_MAX_OBS))
+    strides = []
+    for p, ev in ((F, (h, h)), (H, (h, o))):
+        assert p.dtype == init.dtype and p.is_contiguous() and tuple(p.shape[2:]) == ev \
+            and p.shape[0] in (1, B) and p.shape[1] in (1, T), \
+            "linear_hmm_draw: F [B | 1, T | 1, hidden, hidden], H [B | 1, T | 1, hidden, obs] contiguous of the " \
+            "noise's dtype, got %s" % (tuple(p.shape),)
+        strides += [0 if p.shape[0] == 1 else p.shape[1] * ev[0] * ev[1], 0 if p.shape[1] == 1 else ev[0] * ev[1]]
+    for t, shape in ((init, (S, B, h)), (e, (S, B, T, h)), (n, (S, B, T, o))):
+        assert tuple(t.shape) == shape and t.dtype == init.dtype and t.is_contiguous(), \
+            "linear_hmm_draw: init [S, B, hidden], e [S, B, T, hidden], n [S, B, T, obs] contiguous of one dtype"
+    new = lambda *shape: torch.empty(shape, dtype=init.dtype, device=init.device)     # noqa: E731
+    y = new(S, B, T, o)
+    z = new(S, B, T, h) if need_states else None
+    check(_lib.load().pa_linear_hmm_draw(_dtype(init), _ptr(F), strides[0], strides[1], _ptr(H), strides[2],
+                                         strides[3], B, T, h, o, S, _ptr(init), _ptr(e), _ptr(n), _ptr(y), _ptr(z),
+                                         _stream()))
+    return y, z
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.
