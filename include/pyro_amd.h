@@ -1055,6 +1055,20 @@ int pa_linear_hmm_draw(int dtype, const void* F, int64_t F_stride_batch, int64_t
                        int64_t obs, int64_t S, const void* init, const void* e, const void* n, void* y, void* z,
                        pa_stream_t stream);
 
+/* ---- csrc/forecast_scores.hip: mean, lower median and CRPS of a sample forecast in one pass ---------------------
+ * Replaces crps_empirical (pyro/ops/stats.py: a sort of [S, M] along the sample axis, differences, weights, two
+ * reductions) together with the median(0) of eval_mae and the mean(0) of eval_rmse
+ * (pyro/contrib/forecast/evaluate.py) with ONE launch on the caller's stream that reads pred once.
+ * pred [S, M] contiguous, truth [M]; mean, median, crps [M] of the same dtype (f32 / f64):
+ *   mean   = sum_i p_i / S
+ *   median = p_((S - 1) / 2) of the sorted column (torch's median(0).values)
+ *   crps   = sum_i |p_i - y| / S - sum_{i=1..S-1} (p_(i+1) - p_(i)) i (S - i) / S^2
+ * the sums in float64.  A column with a NaN sample or a NaN truth is NaN in all three outputs, and no other column
+ * is; +-inf follows IEEE through the formula.  No workspace, no atomics: bit-reproducible.
+ * 1 <= S <= 1024, else PA_ERR_UNSUPPORTED.  M = 0: PA_OK without a launch. */
+int pa_forecast_scores(int dtype, const void* pred, const void* truth, int64_t S, int64_t M, void* mean, void* median,
+                       void* crps, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

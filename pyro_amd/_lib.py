@@ -354,6 +354,8 @@ _SIGNATURES = {
     "pa_linear_hmm_draw": (c_int, [c_int] + [c_void_p, c_int64, c_int64] * 2                      # F H
                            + [c_int64] * 5 + [c_void_p] * 3                                       # B T hidden obs S, noise
                            + [c_void_p, c_void_p, c_void_p]),                                     # y, z, stream
+    "pa_forecast_scores": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64]                   # pred truth S M
+                           + [c_void_p] * 4),                                                     # mean median crps, stream
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -635,6 +635,22 @@ std::tuple<at::Tensor, std::vector<at::Tensor>> linear_hmm_draw(const at::Tensor
   return {y, states};
 }
 
+// mean, lower median and CRPS of a sample forecast in one launch that reads pred once (pyro/ops/stats.py
+// crps_empirical with the median(0) and mean(0) of pyro/contrib/forecast/evaluate.py): pred [S, M] contiguous,
+// truth [M] -> (mean, median, crps) [M] each
+std::tuple<at::Tensor, at::Tensor, at::Tensor> forecast_scores(const at::Tensor& pred, const at::Tensor& truth) {
+  const int dt = dtype_of(pred, "forecast_scores");
+  TORCH_CHECK(pred.dim() == 2 && pred.is_contiguous() && pred.size(0) >= 1 && truth.is_cuda() && truth.dim() == 1 &&
+                  truth.is_contiguous() && truth.scalar_type() == pred.scalar_type() && truth.size(0) == pred.size(1),
+              "pyro_amd::forecast_scores: pred [S, M] and truth [M] contiguous of one dtype, S >= 1");
+  const int64_t S = pred.size(0), M = pred.size(1);
+  at::Tensor out = at::empty({3, M}, pred.options());
+  check(pa_forecast_scores(dt, pred.data_ptr(), truth.data_ptr(), S, M, out[0].data_ptr(), out[1].data_ptr(),
+                           out[2].data_ptr(), current_stream()),
+        "forecast_scores");
+  return {out[0], out[1], out[2]};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -824,6 +840,7 @@ TORCH_LIBRARY(pyro_amd, m) {
         "(Tensor x, Tensor[] states)");
   m.def("linear_hmm_draw(Tensor trans, Tensor obs, int T, Tensor init, Tensor e, Tensor n, bool need_states) -> "
         "(Tensor y, Tensor[] states)");
+  m.def("forecast_scores(Tensor pred, Tensor truth) -> (Tensor mean, Tensor median, Tensor crps)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -858,6 +875,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("gaussian_hmm_smooth", &gaussian_hmm_smooth);
   m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);
   m.impl("linear_hmm_draw", &linear_hmm_draw);
+  m.impl("forecast_scores", &forecast_scores);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

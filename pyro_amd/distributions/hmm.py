@@ -476,7 +476,8 @@ class GaussianHMM(TorchDistribution):
         return self._kernel_parts(batch) + [value]
 
     def _kernel_parts(self, batch):
-        """The parts in the layouts of kernels.gaussian_hmm_fwd_bwd: a parameter whose batch dims are all 1 stays
+        """The parts in the layouts of kernels.gaussian_hmm_fwd_bwd: a parameter whose batch dims are all 1 or all
+        expanded (stride 0: what broadcasting a shared location against a per-sequence scale leaves behind) stays
         shared ([1, ...], batch stride 0), any other is expanded to the B sequences; the time axis keeps its size."""
         B = 1
         for n in batch:
@@ -485,8 +486,8 @@ class GaussianHMM(TorchDistribution):
         for i, (p, nd) in enumerate(zip(self._parts, (1, 2, 2, 1, 2, 2, 1, 2))):
             tail = p.shape[-nd - (1 if i >= 2 else 0):]
             lead = p.shape[:p.dim() - len(tail)]
-            if all(n == 1 for n in lead):
-                out.append(p.reshape((1,) + tuple(tail)).contiguous())
+            if all(n == 1 or (n > 1 and s == 0) for n, s in zip(lead, p.stride())):
+                out.append(p[(0,) * len(lead)].reshape((1,) + tuple(tail)).contiguous())
             else:
                 out.append(p.expand(batch + tuple(tail)).reshape((B,) + tuple(tail)).contiguous())
         return out

@@ -1063,6 +1063,30 @@ def linear_hmm_draw(F, H, T, init, e, n, need_states=False):
     return y, z
 
 
+FORECAST_SCORES_MAX_SAMPLES = 1024        # (csrc/forecast_scores.hip FS_MAX_SAMPLES)
+FORECAST_SCORES_STRIPS = ((128, 32), (1024, 16))      # (largest S, strip width C) of the kernel's buckets
+
+
+def forecast_scores(pred, truth):
+    """Mean, lower median and CRPS of a sample forecast in ONE launch (pa_forecast_scores) that reads ``pred``
+    once: ``pred`` [S, M] contiguous, ``truth`` [M] of its dtype (f32 / f64) -> (mean [M], median [M], crps [M]) with
+    median = torch's ``pred.median(0).values`` bit for bit and crps = mean_i |p_i - y| - sum_i (p_(i+1) - p_(i))
+    i (S - i) / S^2, the sums in float64.  A column with a NaN sample or a NaN truth is NaN in all three, alone.
+    Nothing here is differentiable.  S over FORECAST_SCORES_MAX_SAMPLES raises Unsupported."""
+    _require_gpu(pred, truth)
+    assert pred.dim() == 2 and truth.dim() == 1 and truth.shape[0] == pred.shape[1] and pred.shape[0] >= 1, \
+        "forecast_scores: pred [S, M], truth [M], S >= 1, got %s and %s" % (tuple(pred.shape), tuple(truth.shape))
+    assert pred.dtype == truth.dtype and pred.is_contiguous() and truth.is_contiguous(), \
+        "forecast_scores: pred and truth contiguous of one dtype"
+    S, M = pred.shape
+    if S > FORECAST_SCORES_MAX_SAMPLES:
+        raise Unsupported("pyro_amd: forecast_scores: S=%d over the limit of %d" % (S, FORECAST_SCORES_MAX_SAMPLES))
+    out = torch.empty((3, M), dtype=pred.dtype, device=pred.device)
+    check(_lib.load().pa_forecast_scores(_dtype(pred), _ptr(pred), _ptr(truth), S, M, _ptr(out[0]), _ptr(out[1]),
+                                         _ptr(out[2]), _stream()))
+    return out[0], out[1], out[2]
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.

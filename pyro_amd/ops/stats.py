@@ -136,6 +136,62 @@ def hpdi(input, prob, dim=0):
     return torch.cat([lo, hi], dim)
 
 
+FUSED_FORECAST_SCORES = True      # device f32 / f64 samples, S <= 1024, no gradient asked for: pa_forecast_scores
+
+
+def _samples_over_truth(pred, truth):
+    """``pred`` as [S, M] over ``truth`` flattened to [M]; the reference's shape rule (stats.py:493-497):
+    pred.shape == (S,) + (1,) * k + truth.shape."""
+    if pred.dim() < 1 or pred.shape[1:] != (1,) * (pred.dim() - truth.dim() - 1) + truth.shape:
+        raise ValueError("Expected pred to have one extra sample dim on left. Actual shapes: {} versus {}"
+                         .format(tuple(pred.shape), tuple(truth.shape)))
+    return pred.reshape(pred.shape[0], -1), truth.reshape(-1)
+
+
+def _fused_forecast_scores(pred, truth):
+    from .. import kernels
+    return (FUSED_FORECAST_SCORES and kernels.on_device(pred) and kernels.on_device(truth)
+            and pred.dtype == truth.dtype and pred.dtype in (torch.float32, torch.float64)
+            and 1 <= pred.shape[0] <= kernels.FORECAST_SCORES_MAX_SAMPLES
+            and not (torch.is_grad_enabled() and (pred.requires_grad or truth.requires_grad)))
+
+
+def _crps_sorted(pred, truth):
+    """The torch formula over [S, ...] samples (reference: stats.py:498-510); differentiable."""
+    num_samples = pred.size(0)
+    if num_samples == 1:
+        return (pred[0] - truth).abs()
+    pred = pred.sort(dim=0).values
+    diff = pred[1:] - pred[:-1]
+    lower = torch.arange(1, num_samples, device=pred.device, dtype=pred.dtype)
+    weight = (lower * (num_samples - lower)).reshape((-1,) + (1,) * (diff.dim() - 1))
+    return (pred - truth).abs().mean(0) - (diff * weight).sum(0) / num_samples ** 2
+
+
+def forecast_scores(pred, truth):
+    """(mean, lower median, crps) of the samples ``pred`` of shape (S,) + (1,) * k + truth.shape, each of
+    ``truth.shape``: ONE launch that reads ``pred`` once where the kernel route applies (kernels.forecast_scores),
+    ``pred.mean(0)``, ``pred.median(0).values`` and the torch formula of crps_empirical otherwise."""
+    flat, y = _samples_over_truth(pred, truth)
+    if _fused_forecast_scores(flat, y):
+        from .. import kernels
+        return tuple(t.reshape(truth.shape) for t in kernels.forecast_scores(flat.contiguous(), y.contiguous()))
+    return (flat.mean(0).reshape(truth.shape), flat.median(0).values.reshape(truth.shape),
+            _crps_sorted(flat, y).reshape(truth.shape))
+
+
+def crps_empirical(pred, truth):
+    """CRPS* = E|pred - truth| - E|pred - pred'| / 2 of the samples ``pred`` of shape (S,) + (1,) * k + truth.shape
+    against ``truth``, in O(S log S) (reference: stats.py:466-510) -> truth.shape.  Device f32 / f64 samples with
+    S <= 1024 that need no gradient take the one-pass kernel (FUSED_FORECAST_SCORES); everything else the
+    differentiable torch formula."""
+    flat, y = _samples_over_truth(pred, truth)
+    if _fused_forecast_scores(flat, y):
+        from .. import kernels
+        return kernels.forecast_scores(flat.contiguous(), y.contiguous())[2].reshape(truth.shape)
+    return _crps_sorted(flat, y).reshape(truth.shape)
+
+
 def _cummin(input):
     """Cumulative minimum along dim 0 (the reference builds an N x N mask for it, stats.py:142-159)."""
     return torch.cummin(input, dim=0)[0]
