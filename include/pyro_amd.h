@@ -1069,6 +1069,23 @@ int pa_linear_hmm_draw(int dtype, const void* F, int64_t F_stride_batch, int64_t
 int pa_forecast_scores(int dtype, const void* pred, const void* truth, int64_t S, int64_t M, void* mean, void* median,
                        void* crps, pa_stream_t stream);
 
+/* ---- csrc/time_transform.hip: orthonormal DCT-II / Haar transforms along a time axis, one launch ---------------
+ * Replaces dct / idct (pyro/ops/tensor_utils.py: about fifteen torch operators around an rfft each) and
+ * haar_transform / inverse_haar_transform (a Python recursion of log2 N rounds of slicing and cat) with ONE launch
+ * on the caller's stream.  x, y: distinct, contiguous [outer, n, inner] of one dtype (f32 / f64); the transform
+ * runs along n for each of the outer * inner series.
+ *   op 0  dct    y_k = s_k sum_j x_j cos(pi (2j + 1) k / 2n),  s_0 = sqrt(1/n), s_k = sqrt(2/n)
+ *   op 1  idct   its inverse (= its transpose)
+ *   op 2  haar   the layout of the reference's recursion: per level, with m = len / 2, [lo(m), hi(m), tail(len - 2m)],
+ *                hi = (even - odd) / sqrt 2, lo = (even + odd) / sqrt 2 transformed further while m >= 2
+ *   op 3  inverse haar (= its transpose)
+ * All four are orthonormal, so the gradient of op 0 / 1 / 2 / 3 is op 1 / 0 / 3 / 2 of the incoming gradient.
+ * Direct sums in the tensor's dtype against a quarter-wave cosine table in LDS (no n x n matrix), Haar levels in LDS.
+ * No workspace, no atomics: bit-reproducible; a NaN stays inside its own series.
+ * n <= 2048, else PA_ERR_UNSUPPORTED.  outer, n or inner = 0: PA_OK without a launch. */
+int pa_time_transform(int dtype, int op, const void* x, void* y, int64_t outer, int64_t n, int64_t inner,
+                      pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -356,6 +356,8 @@ _SIGNATURES = {
                            + [c_void_p, c_void_p, c_void_p]),                                     # y, z, stream
     "pa_forecast_scores": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64]                   # pred truth S M
                            + [c_void_p] * 4),                                                     # mean median crps, stream
+    "pa_time_transform": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,     # dtype op x y outer n inner
+                                  c_void_p]),                                                       # stream
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -6,9 +6,13 @@ The noise distribution is where this package's state-space kernels come in: a ``
 is scored by ONE launch of the Kalman kernel per loss evaluation (util.reshape_batch keeps shared parameters shared),
 and a forecast is that class's ``prefix_condition`` (the filter's one launch) followed by its fused draw.
 
-Not built, and refused with NotImplementedError when asked for: ``time_reparam`` (the Haar / DCT transforms),
-``dct_gradients`` and ``subsample_aware`` (DCTAdam), ``warm_start``.  There is no HMCForecaster.  Without a marked
-parameter the reference's DCTAdam is ClippedAdam, which is the default optimiser here.
+``HMCForecaster`` fits the same models by NUTS, optionally with every time-local latent sampled in a Haar or DCT basis
+(``time_reparam``; one launch of pa_time_transform per direction and evaluation).
+
+Not built, and refused by ``Forecaster`` with NotImplementedError when asked for: its ``time_reparam`` option (wrap the
+model's ``model`` method in ``poutine.reparam(config=util.time_reparam_dct)`` instead), ``dct_gradients`` and
+``subsample_aware`` (DCTAdam), ``warm_start``.  Without a marked parameter the reference's DCTAdam is ClippedAdam,
+which is the default optimiser here.
 """
 import logging
 from abc import ABCMeta, abstractmethod
@@ -20,8 +24,10 @@ from ...infer import SVI, Trace_ELBO
 from ...infer.autoguide import AutoNormal, init_to_sample
 from ...nn import PyroModule
 from ...optim import ClippedAdam
+from ...poutine.util import site_is_subsample
 from ...primitives import plate, sample, subsample
-from .util import PrefixConditionMessenger, PrefixReplayMessenger, reshape_batch
+from .util import (PrefixConditionMessenger, PrefixReplayMessenger, reshape_batch, time_reparam_dct,
+                   time_reparam_haar)
 
 logger = logging.getLogger(__name__)
 RESIDUAL = "residual"                 # the site ``predict`` makes
@@ -230,6 +236,141 @@ class Forecaster(torch.nn.Module):
             handlers = [PrefixReplayMessenger(latents.trace), PrefixConditionMessenger(self.model._observed_prefix)]
         def run():
             with plate(**particles):
+                return self.model(data, covariates)
+
+        for handler in reversed(handlers):
+            run = handler(run)
+        return run()
+
+
+_TIME_REPARAMS = {"dct": time_reparam_dct, "haar": time_reparam_haar}
+_REPLAY_BATCH = 256          # posterior draws pushed back through the reparameterised model at a time
+
+
+def _latent_sites(trace):
+    return [name for name, site in trace.nodes.items()
+            if site["type"] == "sample" and not site["is_observed"] and not site_is_subsample(site)]
+
+
+class HMCForecaster(torch.nn.Module):
+    """Fits ``model`` to ``(data, covariates)`` by this package's ``MCMC(NUTS(model))`` and then, called with data and
+    LONGER covariates, draws sample forecasts with ``Forecaster``'s contract and output shape.
+
+    ``time_reparam``: None, ``"dct"`` or ``"haar"``: every unobserved site inside the time plate is sampled as its
+    DCT or Haar coefficients along time (``util.time_reparam_dct`` / ``util.time_reparam_haar``), which takes a random
+    walk's correlations out of the geometry NUTS sees.  On the device each evaluation of the model then runs one
+    launch of pa_time_transform per such site and one more for its gradient.  Anything else raises ValueError.
+    ``num_warmup``, ``num_samples``, ``num_chains``, ``dense_mass`` (NUTS ``full_mass``) and ``max_tree_depth`` as
+    the reference's.
+
+    ``jit_compile`` is passed to ``NUTS``, where it captures the sampler's rounds in hipGraphs.  Known open fault: a
+    captured step that contains the GaussianHMM launch has ended in a segmentation fault inside the runtime
+    ("contrib.forecast"); leave it off for a model whose noise is one of the HMM classes.
+
+    Deviation from the reference, on purpose.  The reference replays the REPARAMETERISED model at forecast time, so
+    that PrefixReplayMessenger splices the ``t1`` posterior coefficients onto ``t2 - t1`` prior coefficients in the
+    frequency (or wavelet) domain, which stretches the fitted latent over the longer window.  Here the posterior draws
+    of the ORIGINAL sites are computed once, after the run: the reparameterised model is replayed on the chain's draws
+    in batches and its Delta sites are read.  ``samples`` keeps those time-domain draws ({site: [draws, ...]}, laid out
+    under the particle plate), and a forecast replays the user's own model on them: the time-domain prefix, then the
+    prior for the steps ahead."""
+
+    def __init__(self, model, data, covariates=None, *, num_warmup=1000, num_samples=1000, num_chains=1,
+                 time_reparam=None, dense_mass=False, jit_compile=False, max_tree_depth=10):
+        super().__init__()
+        from ...infer.mcmc import MCMC, NUTS
+        from ...infer.mcmc.util import _guess_max_plate_nesting
+        if time_reparam is not None and time_reparam not in _TIME_REPARAMS:
+            raise ValueError("unknown time_reparam: {!r} (None, 'dct' or 'haar')".format(time_reparam))
+        if covariates is None:
+            covariates = data.new_empty(data.shape[:-1] + (0,))
+        if data.size(-2) != covariates.size(-2):
+            raise ValueError("training needs covariates as long as the data: {} steps against {}"
+                             .format(covariates.size(-2), data.size(-2)))
+        self.model = model
+        sampled = model if time_reparam is None else poutine.reparam(model, config=_TIME_REPARAMS[time_reparam])
+        args = (data, covariates)
+        # dim -1 is the time plate's, also for a model that draws nothing inside it
+        self.max_plate_nesting = max(_guess_max_plate_nesting(model, args, {}),
+                                     _guess_max_plate_nesting(sampled, args, {}), 1)
+        kernel = NUTS(sampled, full_mass=dense_mass, jit_compile=jit_compile, ignore_jit_warnings=True,
+                      max_tree_depth=max_tree_depth, max_plate_nesting=self.max_plate_nesting)
+        mcmc = MCMC(kernel, num_samples=num_samples, warmup_steps=num_warmup, num_chains=num_chains)
+        mcmc.run(*args)
+        self.diagnostics = mcmc.diagnostics
+        self.samples = self._time_domain(sampled, args, mcmc.get_samples())
+        self._num_draws = num_samples * num_chains
+        # the trace forecasts are replayed from: the user's model under a particle plate of size 1, latent sites only
+        with poutine.block(), poutine.trace() as seen, self._particles(1):
+            model(*args)
+        self._trace = seen.trace
+        for name in list(self._trace.nodes):
+            if name not in self.samples:
+                self._trace.remove_node(name)
+
+    def _particles(self, n):
+        return plate("particles", n, dim=-1 - self.max_plate_nesting)
+
+    @torch.no_grad()
+    def _time_domain(self, sampled, args, draws):
+        """The chain's draws of the sites NUTS moved -> draws of the user's model's own latent sites, [draws, ...]
+        under the particle plate: the sampled model is run on the draws, _REPLAY_BATCH at a time, and the values of
+        the original sites (Delta sites where they were reparameterised) are read."""
+        with poutine.block():
+            wanted = _latent_sites(poutine.trace(self.model).get_trace(*args))
+            proto = poutine.trace(sampled).get_trace(*args)
+        batch_ndims = {name: len(proto.nodes[name]["fn"].batch_shape) for name in draws}
+        total = next(iter(draws.values())).size(0) if draws else 0
+        pieces = {name: [] for name in wanted}
+        for start in range(0, total, _REPLAY_BATCH):
+            fixed = {}
+            for name, v in draws.items():
+                v = v[start:start + _REPLAY_BATCH]
+                pad = self.max_plate_nesting - batch_ndims[name]
+                fixed[name] = v.reshape(v.shape[:1] + (1,) * pad + v.shape[1:])
+            n = next(iter(fixed.values())).size(0)
+
+            def run():
+                with self._particles(n):
+                    return sampled(*args)
+            with poutine.block():
+                tr = poutine.trace(poutine.condition(run, data=fixed)).get_trace()
+            for name in wanted:
+                value = tr.nodes[name]["value"]
+                pieces[name].append(value.expand((n,) + tuple(value.shape[1:])) if value.size(0) != n else value)
+        return {name: torch.cat(vs) for name, vs in pieces.items() if vs}
+
+    def __call__(self, data, covariates, num_samples, batch_size=None):
+        """Sample forecasts of the steps ``[t1, t2)``, ``t1 = data.size(-2)`` and ``t2 = covariates.size(-2)``: a
+        tensor of shape ``(num_samples, 1, ..., 1) + data.shape[:-2] + (t2 - t1, data.size(-1))``.  ``batch_size``:
+        draw that many at a time."""
+        return super().__call__(data, covariates, num_samples, batch_size)
+
+    def forward(self, data, covariates, num_samples, batch_size=None):
+        if not isinstance(num_samples, int) or num_samples < 1:
+            raise ValueError("num_samples must be a positive int, got {!r}".format(num_samples))
+        if data.size(-2) > covariates.size(-2):
+            raise ValueError("the covariates end before the data do")
+        if batch_size is not None:
+            sizes = [batch_size] * (num_samples // batch_size) + [num_samples % batch_size]
+            return torch.cat([self._draw(data, covariates, n) for n in sizes if n])
+        return self._draw(data, covariates, num_samples)
+
+    @torch.no_grad()
+    def _draw(self, data, covariates, n):
+        """``n`` forecasts: posterior draws of the latents over the observed steps, picked at random (without
+        replacement while there are enough), then the user's model replayed on them."""
+        weights = torch.ones(self._num_draws, device=data.device)
+        picked = torch.multinomial(weights, n, replacement=n > self._num_draws)
+        for name, node in self._trace.nodes.items():
+            node["value"] = self.samples[name].index_select(0, picked)
+        if data.size(-2) == covariates.size(-2):
+            handlers = [poutine.replay(trace=self._trace)]
+        else:
+            handlers = [PrefixReplayMessenger(self._trace), PrefixConditionMessenger(self.model._observed_prefix)]
+
+        def run():
+            with self._particles(n):
                 return self.model(data, covariates)
 
         for handler in reversed(handlers):

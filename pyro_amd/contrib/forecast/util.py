@@ -6,7 +6,9 @@ pyro.contrib.forecast.util; the code is this package's).
 it to move the time batch dim of a noise distribution out of the way, ``batch_shape + (1,)``.
 ``prefix_condition(d, data)``: ``d`` over ``batch + (t + f, obs)`` given its first ``t`` steps -> ``batch + (f, obs)``.
 ``reshape_transform_batch(t, old_shape, new_shape)``: an element-wise transform whose parameters follow its base
-distribution from ``old_shape`` to ``new_shape``.
+distribution from ``old_shape`` to ``new_shape`` (the DCT and Haar transforms count their dim from the right and stay).
+``time_reparam_dct(msg)``, ``time_reparam_haar(msg)``: configs for ``poutine.reparam`` that sample every unobserved
+site inside the time plate in a frequency or wavelet basis.
 
 How it is organised.  A distribution that is nothing but tensors of its own shape is described ONCE, in TENSOR_FAMILIES:
 class -> ((constructor keyword, event rank of that tensor), ...).  Both operations are then one function applied to
@@ -72,6 +74,34 @@ class PrefixConditionMessenger(Messenger):
         if msg["value"] is not None:
             raise RuntimeError("site {!r} already has a value: nothing is left to forecast".format(msg["name"]))
         msg["fn"] = prefix_condition(msg["fn"], observed)
+
+
+# ---- configs for poutine.reparam -------------------------------------------------------------------------------------
+def _time_reparam(msg, make):
+    if msg["is_observed"] or site_is_subsample(msg):
+        return None
+    for frame in msg["cond_indep_stack"]:
+        if frame.name == "time":
+            return make(dim=frame.dim - msg["fn"].event_dim, experimental_allow_batch=True)
+    return None
+
+
+def time_reparam_dct(msg):
+    """A config for ``poutine.reparam``: every unobserved site inside the plate named ``"time"`` is sampled as its
+    DCT coefficients along time (a ``DiscreteCosineReparam`` along ``frame.dim - fn.event_dim``).  The reference's
+    function of this name returns a HaarReparam and its ``time_reparam_haar`` a DiscreteCosineReparam; that slip is
+    not copied here."""
+    from ...infer.reparam import DiscreteCosineReparam
+    return _time_reparam(msg, DiscreteCosineReparam)
+
+
+def time_reparam_haar(msg):
+    """A config for ``poutine.reparam``: every unobserved site inside the plate named ``"time"`` is sampled as its
+    Haar wavelet coefficients along time (a ``HaarReparam`` along ``frame.dim - fn.event_dim``).  The reference's
+    function of this name returns a DiscreteCosineReparam and its ``time_reparam_dct`` a HaarReparam; that slip is
+    not copied here."""
+    from ...infer.reparam import HaarReparam
+    return _time_reparam(msg, HaarReparam)
 
 
 # ---- distributions that are tensors of their own shape ---------------------------------------------------------------
@@ -284,6 +314,12 @@ def _follow_base(t, old_shape, new_shape):
 
 for _cls in ELEMENTWISE_TRANSFORMS:
     reshape_transform_batch.register(_cls)(_follow_base)
+
+
+@reshape_transform_batch.register(dist.transforms.DiscreteCosineTransform)
+@reshape_transform_batch.register(dist.transforms.HaarTransform)
+def _(t, old_shape, new_shape):
+    return t                                       # dim counts from the right, past the batch dims: nothing moves
 
 
 @reshape_transform_batch.register(transforms.ComposeTransform)

@@ -651,6 +651,25 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> forecast_scores(const at::Tensor&
   return {out[0], out[1], out[2]};
 }
 
+// one of the four orthonormal time transforms along ``dim`` in one launch (pyro/ops/tensor_utils.py dct / idct /
+// haar_transform / inverse_haar_transform): op 0 dct, 1 idct, 2 haar, 3 inverse haar; x contiguous, read as
+// [outer, N, inner] around dim without a transpose -> a tensor of x's shape.  The gradient of op is op ^ 1 of the
+// incoming gradient (the transforms are orthonormal).
+at::Tensor time_transform(const at::Tensor& x, int64_t op, int64_t dim) {
+  const int dt = dtype_of(x, "time_transform");
+  TORCH_CHECK(x.dim() >= 1 && x.is_contiguous() && dim >= -x.dim() && dim < x.dim() && op >= 0 && op <= 3,
+              "pyro_amd::time_transform: x contiguous with at least one dim, dim inside it, op in 0..3");
+  const int64_t d = dim < 0 ? dim + x.dim() : dim;
+  int64_t outer = 1, inner = 1;
+  for (int64_t i = 0; i < d; ++i) outer *= x.size(i);
+  for (int64_t i = d + 1; i < x.dim(); ++i) inner *= x.size(i);
+  at::Tensor y = at::empty_like(x);
+  if (x.numel() == 0) return y;
+  check(pa_time_transform(dt, (int)op, x.data_ptr(), y.data_ptr(), outer, x.size(d), inner, current_stream()),
+        "time_transform");
+  return y;
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -841,6 +860,7 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("linear_hmm_draw(Tensor trans, Tensor obs, int T, Tensor init, Tensor e, Tensor n, bool need_states) -> "
         "(Tensor y, Tensor[] states)");
   m.def("forecast_scores(Tensor pred, Tensor truth) -> (Tensor mean, Tensor median, Tensor crps)");
+  m.def("time_transform(Tensor x, int op, int dim) -> Tensor");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -876,6 +896,7 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("gaussian_hmm_draw", &gaussian_hmm_draw);
   m.impl("linear_hmm_draw", &linear_hmm_draw);
   m.impl("forecast_scores", &forecast_scores);
+  m.impl("time_transform", &time_transform);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

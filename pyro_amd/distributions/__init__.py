@@ -3,7 +3,7 @@
 same way), plus HIP-fused overrides for the hot exponential-family sites.
 """
 import torch
-from torch.distributions import constraints, transforms  # noqa: F401
+from torch.distributions import constraints  # noqa: F401
 from torch.distributions import biject_to, transform_to, kl_divergence  # noqa: F401
 
 from .base import (Delta, ExpandedDistribution, MaskedDistribution, ScoreParts, TorchDistribution,  # noqa: F401
@@ -127,3 +127,4 @@ class Independent(torch.distributions.Independent, TorchDistributionMixin):
         return None if f is None else f(value, scale, mask)
 from .hmm import DiscreteHMM, GammaGaussianHMM, GaussianHMM, IndependentHMM, LinearHMM  # noqa: E402,F401
 __all__ += ["DiscreteHMM", "GammaGaussianHMM", "GaussianHMM", "IndependentHMM", "LinearHMM"]
+from . import transforms  # noqa: E402,F401  (torch.distributions.transforms plus DiscreteCosineTransform, HaarTransform)

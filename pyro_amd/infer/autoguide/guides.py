@@ -15,6 +15,7 @@ from ... import distributions as dist
 from ... import poutine
 from ...distributions.util import sum_rightmost
 from ...primitives import param, plate, sample
+from ...ops.tensor_utils import periodic_repeat
 from ...ops.torch_library import dispatcher_op as _dispatcher_op
 from .initialization import InitMessenger, init_to_feasible, init_to_median
 
@@ -84,18 +85,6 @@ def helpful_support_errors(site):
                 "ProjectedNormal distribution together with a reparameterizer, e.g. "
                 "poutine.reparam(config={{'{0}': ProjectedNormalReparam()}}).".format(name)) from None
         raise e from None
-
-
-def periodic_repeat(tensor, size, dim):
-    """``tensor`` repeated along ``dim`` (period = its size there) and cut to ``size``: how the value
-    drawn for one subsample initialises the parameter of the FULL plate
-    (reference: pyro/ops/tensor_utils.py periodic_repeat)."""
-    if dim >= 0:
-        dim -= tensor.dim()
-    period = tensor.size(dim)
-    repeats = [1] * tensor.dim()
-    repeats[dim] = -(-size // period)
-    return tensor.repeat(*repeats).narrow(dim, 0, size)
 
 
 def _full_plate_value(value, site, event_dim):

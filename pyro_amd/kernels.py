@@ -1087,6 +1087,43 @@ def forecast_scores(pred, truth):
     return out[0], out[1], out[2]
 
 
+TIME_TRANSFORM_MAX_STEPS = 2048           # (csrc/time_transform.hip TT_MAX_STEPS)
+TIME_TRANSFORM_OPS = {"dct": 0, "idct": 1, "haar": 2, "inverse_haar": 3}
+TIME_TRANSFORM_ADJOINT = {0: 1, 1: 0, 2: 3, 3: 2}       # orthonormal: the adjoint of each op is its inverse
+
+
+def time_transform_strip(n, dtype):
+    """Series per workgroup of the time-transform kernels (csrc/time_transform.hip: 2 for f64 over 1024 steps)."""
+    return 2 if dtype == torch.float64 and n > 1024 else 4
+
+
+def time_transform(x, op, dim=-1):
+    """One of the four orthonormal transforms along ``dim`` of ``x`` (f32 / f64, on the device) in ONE launch
+    (pa_time_transform): ``op`` 0 / "dct", 1 / "idct" (type II, scipy's norm="ortho"), 2 / "haar", 3 /
+    "inverse_haar" (the reference's layout).  ``x`` goes to the kernel as [outer, N, inner] without a transpose; a
+    non-contiguous ``x`` is copied first.  The gradient of op is TIME_TRANSFORM_ADJOINT[op] of the incoming gradient.
+    N over TIME_TRANSFORM_MAX_STEPS raises Unsupported; an empty ``x`` makes no launch."""
+    _require_gpu(x)
+    op = TIME_TRANSFORM_OPS.get(op, op)
+    assert op in (0, 1, 2, 3), "time_transform: op is 0..3 or one of %s" % sorted(TIME_TRANSFORM_OPS)
+    assert x.dim() >= 1 and -x.dim() <= dim < x.dim(), "time_transform: dim %d of a %d-d tensor" % (dim, x.dim())
+    dim %= x.dim()
+    n = x.shape[dim]
+    if n > TIME_TRANSFORM_MAX_STEPS:
+        raise Unsupported("pyro_amd: time_transform: N=%d over the limit of %d" % (n, TIME_TRANSFORM_MAX_STEPS))
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    outer, inner = 1, 1
+    for s in x.shape[:dim]:
+        outer *= s
+    for s in x.shape[dim + 1:]:
+        inner *= s
+    check(_lib.load().pa_time_transform(_dtype(x), op, _ptr(x), _ptr(y), outer, n, inner, _stream()))
+    return y
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.

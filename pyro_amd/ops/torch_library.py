@@ -178,6 +178,10 @@ def _register():
     def _(pred, truth):
         return torch.empty_like(truth), torch.empty_like(truth), torch.empty_like(truth)
 
+    @lib.register_fake("pyro_amd::time_transform")
+    def _(x, op, dim):
+        return torch.empty_like(x)
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -660,4 +664,4 @@ def registered_ops():
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
              "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw",
-             "gaussian_hmm_smooth", "gamma_gaussian_hmm", "linear_hmm_draw", "forecast_scores")
+             "gaussian_hmm_smooth", "gamma_gaussian_hmm", "linear_hmm_draw", "forecast_scores", "time_transform")
