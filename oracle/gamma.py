@@ -60,8 +60,9 @@ def _digamma(x):
 def implicit_grad(alpha, x, asymptotic=True):
     """d x / d alpha of the reparameterised standard-Gamma draw (implicit differentiation of the CDF):
     the dual-number power series (x < alpha + 1) / modified-Lentz continued fraction of gamma.hip, and from
-    alpha = 1e4 on its Cornish-Fisher form (``asymptotic=False``: the series everywhere, for the test that
-    pins the one on the other)."""
+    alpha = 1e4 on its Cornish-Fisher form within 8 standard deviations of the mean -- above alpha = 1e8 within
+    a hundredth of the mean (``asymptotic=False``: the series everywhere, for the test that pins the one on
+    the other)."""
     a_all = np.asarray(alpha, dtype=np.float64)
     x_all = np.asarray(x, dtype=np.float64)
     a_all, x_all = np.broadcast_arrays(a_all, x_all)
@@ -70,7 +71,11 @@ def implicit_grad(alpha, x, asymptotic=True):
         a, xv = float(a_all[idx]), float(x_all[idx])
         if not (xv > 0.0 and a > 0.0):
             continue
-        if asymptotic and a >= 1e4 and abs(xv - a) <= 8.0 * np.sqrt(a):
+        if np.isinf(xv) or np.isinf(a):             # (no gradient there; gamma.hip returns NaN at once)
+            out[idx] = np.nan
+            continue
+        dev = abs(xv - a)
+        if asymptotic and a >= 1e4 and (dev <= 8.0 * np.sqrt(a) or (a > 1e8 and dev <= 0.01 * a)):
             # Cornish-Fisher form of the quantile at fixed standard-normal z (gamma.hip), statement for statement
             s = np.sqrt(a)
             z = (xv - a) / s
@@ -88,10 +93,7 @@ def implicit_grad(alpha, x, asymptotic=True):
                 (3.0 * z2 * z2 + 7.0 * z2 - 16.0) / (810.0 * a * a) - \
                 1.5 * (9.0 * z2 * z2 * z + 256.0 * z2 * z - 433.0 * z) / (38880.0 * a * a * s)
             continue
-        if a > 1e8:             # (a tail draw out there) normal limit, see gamma.hip
-            out[idx] = 1.0 + (xv - a) / (2.0 * a)
-            continue
-        budget = 500 + int(16.0 * np.sqrt(a))      # ~ c sqrt(a) terms are needed near x ~ a
+        budget = 500 + int(16.0 * np.sqrt(min(a, 1e12)))      # ~ c sqrt(a) terms are needed near x ~ a
         lx_psi = np.log(xv) - float(_digamma(a))
         if xv < a + 1.0:
             t, dt = 1.0 / a, -1.0 / (a * a)

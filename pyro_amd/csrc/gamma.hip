@@ -65,6 +65,9 @@ __device__ __forceinline__ double gamma_draw(double a, uint64_t seed, uint64_t b
 __device__ __forceinline__ double gamma_implicit_grad(double a, double x, double tol_series = 1e-17,
                                                       double tol_cf = 1e-16) {
   if (!(x > 0.0) || !(a > 0.0)) return 0.0;
+  // an infinite argument has no gradient; NaN at once (the loops below would only reach it after
+  // spending their whole budget: no comparison with a NaN ends them early)
+  if (isinf(x) || isinf(a)) return __builtin_nan("");
   // Both evaluations below need ~ c sqrt(a) terms near x ~ a (the terms only start to fall once
   // n > x - a and then fall like exp(-n^2 / 2a)): the budget grows with sqrt(a) -- a fixed 500 was
   // silently truncated from a ~ 2e4 upwards.  From a = 1e4 on, a draw within 8 standard deviations of
@@ -75,8 +78,13 @@ __device__ __forceinline__ double gamma_implicit_grad(double a, double x, double
   // (cumulants a (n-1)!), z from x by four Newton steps, and d x / d a its partial derivative in a:
   // within 4e-11 of the series at a = 1e4 and better above (the first dropped term is O(a^-3) in the
   // derivative), a dozen flops instead of 2 000 - 160 000 serial iterations.  Tails beyond 8 sigma
-  // keep the series / continued fraction.
-  if (a >= 1e4 && fabs(x - a) <= 8.0 * sqrt(a)) {
+  // keep the series / continued fraction up to a = 1e8.  Above that the form covers |x - a| <= a / 100
+  // (it is a series in r = z / sqrt(a) whose first dropped term is O(r^6): below 1e-15 there), and the
+  // series / continued fraction only run further out, where x / a is bounded away from 1 and they
+  // converge geometrically within a few thousand terms whatever a is.  (The tails of a > 1e8 used to
+  // return the normal limit 1 + (x - a) / 2a: 2.4e-7 off at 12 sigma, and 0.5 for x -> 0.)
+  const double dev = fabs(x - a);
+  if (a >= 1e4 && (dev <= 8.0 * sqrt(a) || (a > 1e8 && dev <= 0.01 * a))) {
     const double s = sqrt(a);
     double z = (x - a) / s;
 #pragma unroll
@@ -95,8 +103,7 @@ __device__ __forceinline__ double gamma_implicit_grad(double a, double x, double
            (3.0 * z2 * z2 + 7.0 * z2 - 16.0) / (810.0 * a * a) -
            1.5 * (9.0 * z2 * z2 * z + 256.0 * z2 * z - 433.0 * z) / (38880.0 * a * a * s);
   }
-  if (a > 1e8) return 1.0 + (x - a) / (2.0 * a);   // (a tail draw out there: the normal limit)
-  const int budget = 500 + (int)(16.0 * sqrt(a));
+  const int budget = 500 + (int)(16.0 * sqrt(a < 1e12 ? a : 1e12));
   const double lx_psi = log(x) - t_digamma<double>(a);
   if (x < a + 1.0) {
     // S = sum_n x^n / (a (a+1) ... (a+n)) and its derivative in a
