@@ -1243,6 +1243,9 @@ int pa_chain_pending(void);
 int pa_chain_tune(int fuse_tail);
 /* chain launches since pa_chain_begin that took the fused form */
 int pa_chain_fused_launches(void);
+/* sites of the last fused chain launch (since pa_chain_begin) that took the one-pass form of
+ * csrc/site_tail.h; 0 when no launch of the recording was fused.  Host-side bookkeeping only. */
+int pa_chain_fast_sites(void);
 /* developer hook: 32 x uint64 of device memory that later chain launches fill with wall-clock
  * (100 MHz) stamps at their phase boundaries (workgroup 0: [0..7], the total's workgroup:
  * [16..23]); NULL switches it off */

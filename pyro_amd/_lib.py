@@ -382,6 +382,7 @@ _SIGNATURES = {
     "pa_chain_debug_stamps": (c_int, [c_void_p]),
     "pa_chain_tune": (c_int, [c_int]),
     "pa_chain_fused_launches": (c_int, []),
+    "pa_chain_fast_sites": (c_int, []),
     "pa_adam_step_publish": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_double, c_double, c_double, c_double, c_double, c_double,
                                      c_double, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,

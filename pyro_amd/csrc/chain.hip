@@ -334,7 +334,9 @@ __global__ __launch_bounds__(1024) void chain_tail_kernel(const ChainArgs a) {
   if (a.have[CH_FIN]) chain_wait(a.jitter, sync, CH_FIN, (uint32_t)part_fin);
   PA_CHAIN_STAMP(2);
   if (total_wg) {
-    total_acc += multi_sum_partial<float, MULTI_THREADS>(KB, 0u, a.fin_dep_mask);
+    // (an empty mask selects EVERY entry: with nothing left for after the wait -- no finalize phase,
+    //  or no entry that reads its outputs -- the first call has summed them all already)
+    if (a.fin_dep_mask != 0u) total_acc += multi_sum_partial<float, MULTI_THREADS>(KB, 0u, a.fin_dep_mask);
     multi_sum_finish<float>(total_acc, a.multi_out, a.multi_coef_all, a.multi_accumulate);
     if (threadIdx.x == 0) step = a.ad_step[0] + 1;
   } else {
@@ -507,6 +509,7 @@ struct ChainState {
   int launches = 0;        // chain launches since pa_chain_begin (diagnostics)
   int phases = 0;          // phases those launches carried
   int fused = 0;           // launches that took the fused form
+  int fast_sites = 0;      // sites of the last fused launch that took the one-pass form (site_tail.h)
   ChainArgs a;
 };
 // One recording per process, NOT per thread: the backward half of a step (the guide's backward,
@@ -546,6 +549,8 @@ static int chain_launch() {
     if (nw > cu_count() - 1) nw = cu_count() - 1;
     hipLaunchKernelGGL(chain_tail_kernel, dim3((unsigned)nw + 1), dim3(1024), 0, s, a);
     c.fused += 1;
+    c.fast_sites = 0;
+    for (int k = 0; k < a.tail_nsites; ++k) c.fast_sites += a.tail[k].fast ? 1 : 0;
   } else {
     hipLaunchKernelGGL(chain_kernel, dim3((unsigned)nw + 1), dim3(1024), 0, s, a);
   }
@@ -729,7 +734,7 @@ int pa_chain_begin(pa_stream_t stream, void* sync_words, size_t sync_bytes) {
   pa::g_chain.on = true;
   pa::g_chain.stream = (hipStream_t)stream;
   pa::g_chain.top = -1;
-  pa::g_chain.launches = pa::g_chain.phases = pa::g_chain.fused = 0;
+  pa::g_chain.launches = pa::g_chain.phases = pa::g_chain.fused = pa::g_chain.fast_sites = 0;
   for (int p = 0; p < pa::CH_PHASES; ++p) pa::g_chain.a.have[p] = 0;
   pa::g_chain.a.sync = (uint32_t*)sync_words;
   return PA_OK;
@@ -765,6 +770,8 @@ int pa_chain_tune(int fuse_tail) {
 }
 
 int pa_chain_fused_launches(void) { return pa::g_chain.fused; }
+
+int pa_chain_fast_sites(void) { return pa::g_chain.fast_sites; }
 
 int pa_chain_debug_stamps(void* stamps32) {
   pa::g_chain_stamps = (uint64_t*)stamps32;

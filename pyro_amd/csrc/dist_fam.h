@@ -45,6 +45,12 @@ template <> __device__ __forceinline__ float pos_log(float x) {
 template <typename T> __device__ __forceinline__ T pos_rcp(T x) { return T(1) / x; }
 template <> __device__ __forceinline__ float pos_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
+// a * b + c in ONE rounding, spelled out.  Left to the compiler, whether d * d - 1 below is contracted depends
+// on the code around the inlined call: the separate launches of multisite_dev.h formed the fma, the one-pass
+// site code of site_tail.h rounded the product first, and the two differed in the last bit of d scale.
+__device__ __forceinline__ float fam_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fam_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
 template <typename T> struct Fam<PA_DIST_NORMAL, T> {  // a=loc b=scale; torch normal.py:88-103
   static __device__ __forceinline__ T lp(T v, T a, T b) {
     const T d = (v - a) * pos_rcp(b);
@@ -54,7 +60,7 @@ template <typename T> struct Fam<PA_DIST_NORMAL, T> {  // a=loc b=scale; torch n
     const T ib = pos_rcp(b), d = (v - a) * ib;
     da = d * ib;
     dv = -da;
-    db = (d * d - T(1)) * ib;
+    db = fam_fma(d, d, T(-1)) * ib;
   }
 };
 // exp(-|a|) and log1p of it.  f32: the hardware exp2 / log2 (v_exp_f32, v_log_f32) -- e in (0, 1]

@@ -172,6 +172,7 @@ __device__ __forceinline__ double multi_sum_partial(uint32_t kbase, uint32_t ski
     if (k < n_entries && wave / wpe < epr) {
       if ((skip_mask >> k & 1u) || (only_mask != 0u && !(only_mask >> k & 1u))) continue;
       const EntryDev e = kernarg_load<EntryDev>(kbase + offsetof(MultiArgs, e) + k * sizeof(EntryDev));
+      if (e.rows * e.cols == 0) continue;   // an empty entry adds nothing (cols = 0: entry_sum divides by it)
       const uint32_t tid = (uint32_t)((wave % wpe) * 64 + lane), nth = (uint32_t)(wpe * 64);
       double s = 0.0;
       PA_DISPATCH_ENTRY(e.dist, s = (entry_sum<D_, T>(e, tid, nth)));

@@ -231,12 +231,15 @@ def chain_flush():
 
 class chain_recording:
     """Context manager: record the chainable launches made inside on torch's current stream and run
-    them as phases of one kernel (see above).  ``stats`` after exit: (chain launches, phases)."""
+    them as phases of one kernel (see above).  ``stats`` after exit: (chain launches, phases);
+    ``fused``: launches that took the fused form; ``fast_sites``: sites of the last fused launch that took
+    the one-pass form."""
 
     def __init__(self, device):
         self.sync = chain_sync_buffer(device)
         self.stats = (0, 0)
         self.fused = 0
+        self.fast_sites = 0
         self._guard = None
 
     def __enter__(self):
@@ -257,6 +260,7 @@ class chain_recording:
             _CHAIN["keep"] = None
             self.stats = (a.value, b.value)
             self.fused = _lib.load().pa_chain_fused_launches()
+            self.fast_sites = _lib.load().pa_chain_fast_sites()
         if exc[0] is None:
             check(rc)
         return False
