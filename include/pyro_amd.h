@@ -1350,7 +1350,8 @@ int pa_mixture_mvn_fwd_bwd(int dtype, const void* x, int64_t N, int D, int K, in
  * doubles (P = 1 or 2 parameters): [0] = S, [1 + k] = R_k, [1 + K + k D + d] = dS/dp0, [1 + K + K D + k D + d] =
  * dS/dp1.  row_lse: B N doubles (the rows' logsumexp between the launches).  Workspace:
  * pa_mixture_event_workspace(dist, K, D, B) bytes, 41.0 MB at K = 64, D = 1024, B = 1 (at most 42 MB at B = 1).
- * Four launches, no host synchronisation, bit-reproducible.  0 from layout / workspace: outside the limits. */
+ * Five launches (the fourth repeats the third where a record came out non-finite), no host synchronisation,
+ * bit-reproducible.  0 from layout / workspace: outside the limits. */
 int64_t pa_mixture_event_layout(int dist, int K, int D);
 size_t pa_mixture_event_workspace(int dist, int K, int D, int64_t B);
 int pa_mixture_event_fwd_bwd(int dtype, int dist, const void* x, int64_t N, int D, int K, int64_t B, const void* a,

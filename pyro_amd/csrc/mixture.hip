@@ -61,21 +61,19 @@ __global__ __launch_bounds__(MIX_THREADS) void mixture_kernel(const T* __restric
     const int64_t row = base + slot;
     const bool valid = row < N;
     const T xv = xs[u];
-    T t = kok ? ak + Fam<DIST, T>::lp(xv, p0k, p1k) : ninf;
-    const T m = mix_allreduce<KP>(t, [](T p, T q) { return mix_max(p, q); });
-    // (a row whose every term is -inf: its logsumexp is -inf and it has no responsibilities)
-    const bool dead = !(m > ninf);
-    const T e = (dead || !kok) ? T(0) : t_exp(t - m);
-    const T ssum = mix_allreduce<KP>(e, [](T p, T q) { return p + q; });
-    // (ssum >= 1 for a live row: the hardware log / reciprocal of the float path are 1 ulp there)
-    const T lse = dead ? ninf : m + pos_log(dead ? T(1) : ssum);
-    const T r = (dead || !valid) ? T(0) : e * pos_rcp(dead ? T(1) : ssum);
+    const T t = kok ? ak + Fam<DIST, T>::lp(xv, p0k, p1k) : ninf;
+    // (a row whose every term is -inf: its logsumexp is -inf and it has no responsibilities; a NaN term: the row's
+    //  logsumexp and every r of the row are NaN, whichever component holds it)
+    T lse, r;
+    mix_row<KP>(t, kok, lse, r);
+    if (!valid) r = T(0);
     T dv, da, db;
     Fam<DIST, T>::grad(xv, p0k, p1k, dv, da, db);
     acc_s += (valid && k == 0) ? lse : T(0);
     acc_a += r;
-    acc_0 += r > T(0) ? r * da : T(0);
-    acc_1 += r > T(0) ? r * db : T(0);
+    // (r == 0 exactly: no gradient, whatever the family's derivative is there; a NaN r is handed on)
+    acc_0 += r == T(0) ? T(0) : r * da;
+    acc_1 += r == T(0) ? T(0) : r * db;
     }
   }
   // lanes of the same k (the wave's RPW row slots), in double
@@ -180,6 +178,7 @@ __global__ __launch_bounds__(MIX_THREADS) void mixture_diag_kernel(const T* __re
     inv[d] = dok ? pos_rcp(sg) : T(0);
     if (dok && kok) ck -= pos_log(sg) + Consts<T>::half_log_2pi;
   }
+  const T* mup = loc + (kok ? (int64_t)k * l_sk : 0);            // where mu[d], d >= D, was read from
   T acc_s = T(0), acc_a = T(0), acc_l[DD], acc_c[DD];
 #pragma unroll
   for (int d = 0; d < DD; ++d) acc_l[d] = acc_c[d] = T(0);
@@ -193,24 +192,33 @@ __global__ __launch_bounds__(MIX_THREADS) void mixture_diag_kernel(const T* __re
     T q = T(0);
 #pragma unroll
     for (int d = 0; d < DD; ++d) {
-      const T xv = xr[d < D ? d : 0];
+      const T xv = *(d < D ? xr + d : mup);         // (nothing past D, whatever x[row][0] is: mu itself, x - mu = 0)
       z[d] = (xv - mu[d]) * inv[d];                 // (inv = 0 past D)
       q += z[d] * z[d];
     }
     const T t = kok ? ck - T(0.5) * q : ninf;
-    const T m = mix_allreduce<KP>(t, [](T p, T r_) { return mix_max(p, r_); });
-    const bool dead = !(m > ninf);
-    const T e = (dead || !kok) ? T(0) : t_exp(t - m);
-    const T ssum = mix_allreduce<KP>(e, [](T p, T r_) { return p + r_; });
-    const T lse = dead ? ninf : m + pos_log(dead ? T(1) : ssum);
-    const T r = (dead || !valid) ? T(0) : e * pos_rcp(dead ? T(1) : ssum);
+    T lse, r;
+    mix_row<KP>(t, kok, lse, r);
+    if (!valid) r = T(0);
     acc_s += (valid && k == 0) ? lse : T(0);
     acc_a += r;
+    // (r == 0 exactly: no gradient, whatever z is there; a NaN r is handed on.  A branch around the sums as they
+    //  always were, not a select inside them: the float32 sums keep the packed form the compiler gives them, and
+    //  ordinary data its bits)
+    if (r != T(0)) {
 #pragma unroll
-    for (int d = 0; d < DD; ++d) {
-      const T w = r * inv[d];
-      acc_l[d] += w * z[d];                         // r (x - loc) / scale^2
-      acc_c[d] += w * (z[d] * z[d] - T(1));         // r ((x - loc)^2 / scale^2 - 1) / scale
+      for (int d = 0; d < DD; ++d) {
+        const T w = r * inv[d];
+        // r (x - loc) / scale^2 and r ((x - loc)^2 / scale^2 - 1) / scale.  (float: the three fused multiply-adds the
+        // compiler formed here before the branch existed, spelled out -- under the branch it shares z z with q instead)
+        if constexpr (sizeof(T) == 4) {
+          acc_l[d] = fam_fma(w, z[d], acc_l[d]);
+          acc_c[d] = fam_fma(w, fam_fma(z[d], z[d], T(-1)), acc_c[d]);
+        } else {
+          acc_l[d] += w * z[d];
+          acc_c[d] += w * (z[d] * z[d] - T(1));
+        }
+      }
     }
   }
   const int64_t gw = (int64_t)blockIdx.x * (MIX_THREADS / 64) + wave;

@@ -25,7 +25,7 @@
 // (xlogy and its derivative as dist_fam.h states them for torch: 0 at a zero coefficient unless the log's argument is
 // NaN.)
 //
-// Four launches:
+// Five launches:
 //   1. prep:     one workgroup per (k, b): c_k in double.
 //   2. lse:      one thread per row, rows in tiles of 256; the tile's x and the staged parameters of 16 components
 //                pass through LDS in chunks of features (one global read of x per 16 components); t_nk of the 16
@@ -37,6 +37,8 @@
 //                each thread owns DB / 16 (k, d) pairs of the block and adds r times the statistic over the tile's
 //                rows (x staged again, per sub-tile), in the input dtype per sub-tile and in double across them.
 //                One record per workgroup: R (feature block 0) and the sums of its pairs.
+//   3b. redo:    launch 3 again for the workgroups whose record came out non-finite, without the rows and components
+//                whose responsibility is exactly 0 (see mixture_event_stats_kernel); the others leave at once.
 //   4. finalize: one wave per (k, 64 features, b): the records added in chunk order in double and the chain rule
 //                in double with the parameters; wave (0, 0, b) adds the lse partials in a fixed order.  No atomics
 //                anywhere: two runs give identical bits.
@@ -118,15 +120,24 @@ __global__ __launch_bounds__(EV_THREADS) void mixture_event_lse_kernel(const T* 
     }
     const double l = s > 0.0 ? m + log(s) : (s == 0.0 ? ninf : s);
     if (n < N) {
-      lse[b * N + n] = l;
-      acc += l + qrow;
+      // (a row term that makes the row's logsumexp NaN -- LogNormal at x = 0: -inf - log 0 -- makes it a NaN row for
+      //  the statistics as well, as a NaN term does)
+      const double lq = l + qrow;
+      lse[b * N + n] = lq != lq ? lq : l;
+      acc += lq;
     }
   }
   const double tot = block_sum_f64(acc, red);
   if (tid == 0) spart[b * gridDim.x + blockIdx.x] = tot;
 }
 
-template <int F, typename T, int DB>
+// REDO (the launch after the plain one): r == 0 exactly -- a dead row, a switched-off or collapsed component -- adds
+// no statistic, whatever the staged value is there; the plain sums form 0 * inf for it (Gamma at x = 0, Normal at
+// x = inf).  A workgroup of the REDO launch leaves at once unless its record came out non-finite, and then adds it
+// again with the zero responsibilities left out (a NaN r is handed on either way).  The guard is not inside the plain
+// sums because it changes how the compiler packs and fuses their float32 multiply-adds, hence the last bits of ordinary
+// data.
+template <int F, typename T, int DB, bool REDO>
 __global__ __launch_bounds__(EV_THREADS) void mixture_event_stats_kernel(const T* __restrict__ x, int64_t N, int D,
                                                                          int K, EvParams P,
                                                                          const double* __restrict__ ck,
@@ -161,6 +172,15 @@ __global__ __launch_bounds__(EV_THREADS) void mixture_event_stats_kernel(const T
 #pragma unroll
     for (int i = 0; i < NP; ++i) qp[j][i] = T(0);
     if (kk < K && d < D) E::par(p0[kk * P.p0_k + d * P.p0_d], p1 ? p1[kk * P.p1_k + d * P.p1_d] : T(0), qp[j]);
+  }
+  if constexpr (REDO) {                                 // (the record the plain launch wrote: R only in block 0)
+    const double* was = rec + (((b * (int64_t)gridDim.y) + blockIdx.y) * gridDim.x + c) * ev_record(DB, NS);
+    int odd = 0;
+    for (int64_t e = tid + (db == 0 ? 0 : EV_KC); e < ev_record(DB, NS); e += EV_THREADS) {
+      const double o = was[e];
+      odd |= !(o - o == 0.0);
+    }
+    if (!__syncthreads_or(odd)) return;                 // (uniform over the workgroup)
   }
   double sacc[PPT][NS];
 #pragma unroll
@@ -215,7 +235,14 @@ __global__ __launch_bounds__(EV_THREADS) void mixture_event_stats_kernel(const T
 #pragma unroll
           for (int i = 0; i < NX; ++i) v[i] = xs[(i * TB + rr) * DB + dl];
 #pragma unroll
-          for (int j = 0; j < PPT; ++j) E::stat(v, qp[j], rs[(k0 + j * KSTEP) * EV_TR + s0 + rr], sp[j]);
+          for (int j = 0; j < PPT; ++j) {
+            if constexpr (REDO) {
+              const T r = rs[(k0 + j * KSTEP) * EV_TR + s0 + rr];
+              if (r != T(0)) E::stat(v, qp[j], r, sp[j]);
+            } else {
+              E::stat(v, qp[j], rs[(k0 + j * KSTEP) * EV_TR + s0 + rr], sp[j]);
+            }
+          }
         }
 #pragma unroll
         for (int j = 0; j < PPT; ++j)
@@ -271,6 +298,9 @@ __global__ __launch_bounds__(EV_FIN_THREADS) void mixture_event_finalize_kernel(
     const T* p1 = P.p1 ? (const T*)P.p1 + b * P.p1_b + k * P.p1_k : nullptr;
     double g[2];
     E::grad(R, s, (double)p0[d * P.p0_d], p1 ? (double)p1[d * P.p1_d] : 0.0, g);
+    // (R == 0 exactly: no row has a responsibility for k, so there is no gradient, whatever the chain rule's factors
+    //  are there -- 0 / 0 at a Poisson rate of 0; a NaN R is handed on)
+    if (R == 0.0) g[0] = g[1] = 0.0;
     o[1 + K + (int64_t)k * D + d] = g[0];
     if (E::NPAR == 2) o[1 + K + (int64_t)K * D + (int64_t)k * D + d] = g[1];
   }
@@ -305,9 +335,12 @@ static int mixture_event_launch(const T* x, int64_t N, int D, int K, int64_t B, 
                      a, a_bs, P, ck);
   hipLaunchKernelGGL((mixture_event_lse_kernel<F, T>), dim3((unsigned)g1, (unsigned)B), dim3(EV_THREADS), 0, s, x, N,
                      D, K, P, (const double*)ck, row_lse, spart);
-  hipLaunchKernelGGL((mixture_event_stats_kernel<F, T, DB>), dim3((unsigned)chunks, (unsigned)(nkc * ndb), (unsigned)B),
-                     dim3(EV_THREADS), 0, s, x, N, D, K, P, (const double*)ck, (const double*)row_lse, rows_per, ndb,
-                     rec);
+  hipLaunchKernelGGL((mixture_event_stats_kernel<F, T, DB, false>),
+                     dim3((unsigned)chunks, (unsigned)(nkc * ndb), (unsigned)B), dim3(EV_THREADS), 0, s, x, N, D, K, P,
+                     (const double*)ck, (const double*)row_lse, rows_per, ndb, rec);
+  hipLaunchKernelGGL((mixture_event_stats_kernel<F, T, DB, true>),
+                     dim3((unsigned)chunks, (unsigned)(nkc * ndb), (unsigned)B), dim3(EV_THREADS), 0, s, x, N, D, K, P,
+                     (const double*)ck, (const double*)row_lse, rows_per, ndb, rec);
   hipLaunchKernelGGL((mixture_event_finalize_kernel<F, T>),
                      dim3((unsigned)K, (unsigned)((D + EV_FIN_THREADS - 1) / EV_FIN_THREADS), (unsigned)B),
                      dim3(EV_FIN_THREADS), 0, s,

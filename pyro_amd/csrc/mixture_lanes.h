@@ -3,6 +3,7 @@
 // aligned lanes.
 #pragma once
 #include "common.h"
+#include "dist_fam.h"
 
 namespace pa {
 
@@ -33,6 +34,23 @@ template <int KP, typename T, typename Op> __device__ __forceinline__ T mix_allr
   if constexpr (KP >= 32) v = op(v, __shfl_xor(v, 16, 64));
   if constexpr (KP >= 64) v = op(v, __shfl_xor(v, 32, 64));
   return v;
+}
+
+// max that hands on a NaN whichever side it is on (both lanes of a butterfly step agree)
+template <typename T> __device__ __forceinline__ T mix_nanmax(T a, T b) { return (a > b || a != a) ? a : b; }
+
+// one row's logsumexp and responsibilities from its KP lanes' terms.  t = -inf on padded lanes.  A row whose every
+// term is -inf: lse = -inf, r = 0; a NaN term: lse and every r of the row NaN.
+template <int KP, typename T>
+__device__ __forceinline__ void mix_row(T t, bool kok, T& lse, T& r) {
+  const T ninf = -t_inf<T>();
+  const T m = mix_allreduce<KP>(t, [](T p, T q) { return mix_nanmax(p, q); });
+  const bool dead = m == ninf;
+  const T e = (dead || !kok) ? T(0) : t_exp(t - m);
+  const T ssum = mix_allreduce<KP>(e, [](T p, T q) { return p + q; });
+  // (ssum >= 1 for a live row: the hardware log / reciprocal of the float path are 1 ulp there)
+  lse = dead ? ninf : m + pos_log(dead ? T(1) : ssum);
+  r = dead ? T(0) : e * pos_rcp(dead ? T(1) : ssum);
 }
 
 }  // namespace pa

@@ -148,7 +148,9 @@ __global__ __launch_bounds__(MVN_THREADS) void mixture_mvn_stats_kernel(const T*
       // (a row whose every term is -inf has no responsibilities; NaN in a row propagates)
       const T r = l == ninf ? T(0) : t_exp(t - l);
 #pragma unroll
-      for (int j = 0; j < DP; ++j) dT[j * TRP + tid] = valid ? d[j] : T(0);
+      // (r == 0 exactly -- a dead row, a switched-off component: nothing of the row enters C or s, whatever d is
+      //  there (0 * inf); a NaN r is handed on)
+      for (int j = 0; j < DP; ++j) dT[j * TRP + tid] = (valid && r != T(0)) ? d[j] : T(0);
       rs[tid] = r;
     }
     __syncthreads();

@@ -26,22 +26,8 @@ namespace pa {
 
 constexpr int MIXR_U = 4;     // iterations whose loads of x and a are requested together
 
-// max that hands on a NaN whichever side it is on (both lanes of a butterfly step agree)
-template <typename T> __device__ __forceinline__ T mixr_max(T a, T b) { return (a > b || a != a) ? a : b; }
-
-// one row's logsumexp and responsibilities from its KP lanes' terms.  t = -inf on padded lanes.  A row whose every
-// term is -inf: lse = -inf, r = 0; a NaN term: lse and every r of the row NaN.
-template <int KP, typename T>
-__device__ __forceinline__ void mixr_row(T t, bool kok, T& lse, T& r) {
-  const T ninf = -t_inf<T>();
-  const T m = mix_allreduce<KP>(t, [](T p, T q) { return mixr_max(p, q); });
-  const bool dead = m == ninf;
-  const T e = (dead || !kok) ? T(0) : t_exp(t - m);
-  const T ssum = mix_allreduce<KP>(e, [](T p, T q) { return p + q; });
-  // (ssum >= 1 for a live row: the hardware log / reciprocal of the float path are 1 ulp there)
-  lse = dead ? ninf : m + pos_log(dead ? T(1) : ssum);
-  r = dead ? T(0) : e * pos_rcp(dead ? T(1) : ssum);
-}
+// (mix_row of mixture_lanes.h: a row whose every term is -inf has lse = -inf and r = 0; a NaN term makes lse and every
+//  r of the row NaN)
 
 template <int DIST, typename T, int KP>
 __global__ __launch_bounds__(MIX_THREADS) void mixture_rows_kernel(const T* __restrict__ x, int64_t N, int K,
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(MIX_THREADS) void mixture_rows_kernel(const T* __re
       const T xv = xs[u];
       const T t = kok ? as[u] + Fam<DIST, T>::lp(xv, p0k, p1k) : ninf;
       T lse, r;
-      mixr_row<KP>(t, kok, lse, r);
+      mix_row<KP>(t, kok, lse, r);
       if (!valid) r = T(0);
       if (da != nullptr && valid && kok) da[row * K + k] = r;
       T dv, g0, g1;
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(MIX_THREADS) void mixture_rows_diag_kernel(const T*
       }
       const T t = kok ? as[u] + ck - T(0.5) * q : ninf;
       T lse, r;
-      mixr_row<KP>(t, kok, lse, r);
+      mix_row<KP>(t, kok, lse, r);
       if (!valid) r = T(0);
       if (da != nullptr && valid && kok) da[row * K + k] = r;
       acc_s += (valid && k == 0) ? lse : T(0);
