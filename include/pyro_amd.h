@@ -393,6 +393,40 @@ int pa_glm_bernoulli_fwd_bwd(const float* X, const float* y, const float* w, con
                              float* ll, float* gw, float* gb, void* workspace,
                              size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- plated Normal / StudentT / Poisson / Binomial regression sites (csrc/glm_family.hip) -----
+ * The frame of pa_glm_bernoulli_fwd_bwd variant 1 (exact f32 MFMA, one pass over X, nothing of size
+ * P x N) with the element-wise step supplied by the family.  Replaces, for an observed site under
+ * pyro.plate with P vectorised particles,
+ *   Normal(w @ X^T + b, sigma) / StudentT(nu, w @ X^T + b, sigma) / Poisson(exp(w @ X^T + b)) /
+ *   Binomial(n, logits = w @ X^T + b)
+ * the matmul, log_prob, scale_and_mask, .sum() and their autograd duals.
+ * With eta_pn = w_p . x_n + b_p, m_n the mask:
+ *   s[P]       = scale * sum_n m_n t(y_n, eta_pn; aux_p)      t: the DATA-DEPENDENT part of the log density
+ *   gw[P,D]    = d s / d w,   gb[P] = d s / d b,   gaux[P,A] = d s / d aux
+ *   cnt[1]     = sum_n m_n (float64)
+ * family                    aux[P,A]            t
+ *   PA_GLM_NORMAL           sigma      (A = 1)  -z^2 / 2,  z = (y - eta) / sigma
+ *   PA_GLM_STUDENT_T        nu, sigma  (A = 2)  -(nu + 1)/2 log1p(z^2 / nu)
+ *   PA_GLM_POISSON_LOG      NULL       (A = 0)  y eta - exp(eta) - lgamma(y + 1)
+ *   PA_GLM_BINOMIAL_LOGITS  NULL       (A = 0)  y eta - n softplus(eta) + lgamma(n+1) - lgamma(y+1) - lgamma(n-y+1)
+ * The normalisers that depend on the particle only (-log sigma - log(2 pi)/2; the Gamma-function
+ * terms of StudentT) are NOT included: the caller adds scale * cnt * c(aux_p).
+ * Binomial: count[N] f32 per row, or NULL and count_scalar for every row.  gaux may be NULL when A = 0.
+ * mask[N] uint8 (NULL = all true): a masked row contributes exactly 0 whatever it holds (inf, NaN).
+ * max_blocks > 0 caps the grid's x extent (0: the kernel's own choice).
+ * Deterministic (per-workgroup partial records, fp64 finalize); f32, 1 <= D <= 128, else
+ * PA_ERR_UNSUPPORTED (workspace: 0).  N = 0: zeros without a kernel launch. */
+#define PA_GLM_NORMAL 0
+#define PA_GLM_STUDENT_T 1
+#define PA_GLM_POISSON_LOG 2
+#define PA_GLM_BINOMIAL_LOGITS 3
+size_t pa_glm_family_workspace(int family, int64_t N, int64_t D, int64_t P, int max_blocks);
+int pa_glm_family_fwd_bwd(int family, const float* X, const float* y, const float* w, const float* b,
+                          const float* aux, const float* count, double count_scalar,
+                          const uint8_t* mask, double scale, int64_t N, int64_t D, int64_t P,
+                          int max_blocks, float* s, float* gw, float* gb, float* gaux, double* cnt,
+                          void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* ---- the hierarchical GLM site on the plane image (BASELINE config 5) -------------------------
  * Rows sorted by group, cut into segments seg[nseg][3] = {row_begin, row_end, group} (device
  * int64; as pa_glm_bernoulli_grouped_fwd_bwd).  The image places every segment on a super-tile

@@ -26,6 +26,9 @@ DIST_GAMMA = 6
 DIST_BETA = 7
 DIST_POISSON = 8
 DIST_BINOMIAL_LOGITS = 9
+# families of pa_glm_family_fwd_bwd (PA_GLM_* of include/pyro_amd.h) and their aux columns
+GLM_NORMAL, GLM_STUDENT_T, GLM_POISSON_LOG, GLM_BINOMIAL_LOGITS = 0, 1, 2, 3
+GLM_AUX_COLUMNS = {GLM_NORMAL: 1, GLM_STUDENT_T: 2, GLM_POISSON_LOG: 0, GLM_BINOMIAL_LOGITS: 0}
 DIST_KL_NORMAL_LOC = 10
 DIST_KL_NORMAL_SCALE = 11
 
@@ -122,6 +125,11 @@ _SIGNATURES = {
     "pa_glm_bernoulli_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_double, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pa_glm_family_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int]),
+    "pa_glm_family_fwd_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_double, c_void_p, c_double, c_int64, c_int64, c_int64, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "pa_tall_linear": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                c_void_p, c_void_p]),
     "pa_tall_linear_act": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,

@@ -22,7 +22,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # MFMAs; packed f32 instructions (which the SLP vectoriser forms from adjacent scalar operations) do
 # not overlap the MFMAs on gfx950 and cost 2-4x a plain instruction next to them
 # (tools/probes/issue_probe.hip), so that file is built without SLP vectorisation.
-FILE_FLAGS = {"glm.hip": ["-fno-slp-vectorize"]}
+# glm_family.hip is the same frame with f32 MFMAs: same flag.
+FILE_FLAGS = {"glm.hip": ["-fno-slp-vectorize"], "glm_family.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("PA_CHAIN_LATENCY_PROBE"):          # developer probe (tools/chain_stamps.py)
     FILE_FLAGS["chain.hip"] = ["-DPA_CHAIN_LATENCY_PROBE"]
 

@@ -10,13 +10,13 @@ from .base import (Delta, ExpandedDistribution, MaskedDistribution, ScoreParts, 
                    TorchDistributionMixin, Unit)
 from .families import (Bernoulli, Beta, Binomial, Dirichlet, Exponential, Gamma,  # noqa: F401
                        GroupedLinearLogits, HalfCauchy, HalfNormal, LinearLogits, LogNormal, Normal,
-                       Poisson, grouped_linear_logits, linear_logits)
+                       Poisson, StudentT, grouped_linear_logits, linear_logits)
 from .util import enable_validation, is_validation_enabled  # noqa: F401
 from . import kl as _kl  # noqa: F401,E402  (registers the reference's extra kl_divergence pairs)
 
 # ---- everything else: torch.distributions + mixin, arithmetic by ATen on the GPU ----------------
 _FUSED = {"Normal", "Bernoulli", "HalfCauchy", "HalfNormal", "LogNormal", "Exponential",
-          "Gamma", "Beta", "Poisson", "Binomial", "Dirichlet"}
+          "Gamma", "Beta", "Poisson", "Binomial", "Dirichlet", "StudentT"}
 __all__ = ["Delta", "Unit", "MaskedDistribution", "TorchDistribution", "ScoreParts",
            "LinearLogits", "linear_logits", "GroupedLinearLogits", "grouped_linear_logits"] + sorted(_FUSED)
 

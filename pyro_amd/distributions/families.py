@@ -110,7 +110,15 @@ class Normal(_FusedElementwise, torch.distributions.Normal, TorchDistributionMix
     # whose value IS that draw is scored in closed form (fused_linear_term below).
     _drawn = None
 
+    def __new__(cls, loc=None, scale=None, validate_args=None):
+        # unmodified model text Normal(w @ X.t() + b, sigma): the plated linear regression if its shape says so;
+        # otherwise torch's constructor evaluates the product (broadcast_all is a torch function)
+        site = _linear_predictor_site(_lib.GLM_NORMAL, loc, "identity", (scale,))
+        return site if site is not None else super().__new__(cls)
+
     def __init__(self, loc, scale, validate_args=None):
+        if isinstance(loc, _lazy._DEFERRED):      # not the fused site (see __new__): evaluate what was written
+            loc = loc.materialize()
         loc, scale = _on_device(loc, scale)
         super().__init__(loc, scale, validate_args=validate_args)
 
@@ -398,6 +406,11 @@ class _CountFamily(_GammaFunctionFamily):
 class Poisson(_CountFamily, torch.distributions.Poisson, TorchDistributionMixin):
     _dist_id = _lib.DIST_POISSON
 
+    def __new__(cls, rate=None, validate_args=None):
+        # Poisson(torch.exp(w @ X.t() + b)): count regression with the log link
+        site = _linear_predictor_site(_lib.GLM_POISSON_LOG, rate, "exp", ())
+        return site if site is not None else super().__new__(cls)
+
     def _params(self):
         return self.rate, None
 
@@ -407,9 +420,24 @@ class Binomial(_CountFamily, torch.distributions.Binomial, TorchDistributionMixi
     ``approx_log_prob_tol = 0``, its default."""
     _dist_id = _lib.DIST_BINOMIAL_LOGITS
 
+    def __new__(cls, total_count=1, probs=None, logits=None, validate_args=None):
+        # Binomial(n, logits=w @ X.t() + b): grouped-trials logistic regression
+        site = None if probs is not None else \
+            _linear_predictor_site(_lib.GLM_BINOMIAL_LOGITS, logits, "identity", (), total_count)
+        return site if site is not None else super().__new__(cls)
+
     def _params(self):
         logits, n = self.logits, self.total_count
         return logits, (n if n.dtype == logits.dtype else n.to(logits.dtype))
+
+
+class StudentT(torch.distributions.StudentT, TorchDistributionMixin):
+    """torch.distributions.StudentT with the Pyro mixin interface; ``StudentT(nu, w @ X.t() + b, sigma)`` on a
+    deferred product is the plated robust regression site."""
+
+    def __new__(cls, df=None, loc=0.0, scale=1.0, validate_args=None):
+        site = _linear_predictor_site(_lib.GLM_STUDENT_T, loc, "identity", (df, scale))
+        return site if site is not None else super().__new__(cls)
 
 
 class LinearLogits:
@@ -654,6 +682,161 @@ class _BernoulliLinear(TorchDistribution):
         else:
             ll = fused.glm_bernoulli_ll(lz.X, value.contiguous(), w2, b1, mask, scale)
         return ll.reshape(lz.shape[:-1])
+
+
+# ---- plated Normal / StudentT / Poisson / Binomial regression sites -------------------------------------------
+FUSED_GLM_FAMILIES = True       # False: the four constructors never return the fused site (bench baseline)
+
+
+def _aux_parameter(v, lz):
+    """A parameter of the site that depends on the particle only -- a Python number, a 0-dim tensor or a [..., 1]
+    tensor next to the lazy predictor's particle dims -- as a tensor of the predictor's dtype and device; None if
+    it is anything else (a per-row tensor, another dtype or device)."""
+    if isinstance(v, bool):
+        return None
+    if isinstance(v, (int, float)):
+        return device_constant(v, lz.dtype, lz.device)
+    if not isinstance(v, torch.Tensor):
+        return None
+    v = _lazy._plain(v)
+    if v.device != lz.device or v.dim() > len(lz.shape):
+        return None
+    if not v.is_floating_point():
+        if v.dim() != 0:
+            return None
+        v = v.to(lz.dtype)
+    if v.dtype != lz.dtype or (v.dim() > 0 and v.shape[-1] != 1):
+        return None
+    return v
+
+
+def _linear_predictor_site(family, operand, link, aux, total_count=None):
+    """The fused site for ``family`` if ``operand`` is a deferred product with that link and the remaining
+    parameters depend on the particle only; else None (the caller's ordinary constructor then evaluates what the
+    model wrote)."""
+    if not FUSED_GLM_FAMILIES or not isinstance(operand, _lazy.DeferredMatmul):
+        return None
+    pred = operand.as_linear_predictor()
+    if pred is None or pred[1] != link:
+        return None
+    lz = pred[0]
+    aux_t = tuple(_aux_parameter(a, lz) for a in aux)
+    if any(a is None for a in aux_t):
+        return None
+    count = None
+    if family == _lib.GLM_BINOMIAL_LOGITS:
+        n = total_count
+        if isinstance(n, torch.Tensor) and n.dim() == 1 and n.shape[0] == lz.shape[-1] and lz.shape[-1] > 1:
+            if n.requires_grad or n.device != lz.device or n.dtype == torch.bool:
+                return None
+            count = _lazy._plain(n)                      # a constant count per row
+        elif isinstance(n, torch.Tensor) and n.dim() == 0 and not n.requires_grad and n.device == lz.device:
+            count = _lazy._plain(n)
+        elif isinstance(n, (int, float)) and not isinstance(n, bool):
+            count = float(n)
+        else:
+            return None
+    try:
+        lead = torch.broadcast_shapes(lz.shape[:-1], *[a.shape[:-1] for a in aux_t if a.dim() > 0])
+    except RuntimeError:
+        return None
+    return _LinearPredictor(family, lz, aux_t, count, torch.Size(lead))
+
+
+class _LinearPredictor(TorchDistribution):
+    """Normal / StudentT / Poisson / Binomial whose location (rate, logits) is a lazy linear predictor: the plated
+    regression observed site.  ``aux``: (sigma,) | (nu, sigma) | (); ``count``: Binomial's total_count (a number,
+    a 0-dim tensor or a constant [N] tensor).  The operand is ``predictor``, NOT ``lazy``: consumers that
+    recognise the Bernoulli site by that attribute (the direct NUTS potential, infer/mcmc/direct.py) must not take
+    this class for it."""
+
+    has_enumerate_support = False
+
+    def __init__(self, family, lazy, aux, count, lead, validate_args=None):
+        self.family, self.predictor, self.aux, self.count = family, lazy, aux, count
+        super().__init__(torch.Size(lead) + lazy.shape[-1:], torch.Size(), validate_args=False)
+
+    @property
+    def arg_constraints(self):
+        return _ORDINARY[self.family]().arg_constraints
+
+    @property
+    def support(self):
+        if self.family == _lib.GLM_BINOMIAL_LOGITS:
+            return constraints.integer_interval(0, self.count)
+        return _ORDINARY[self.family]().support
+
+    def ordinary(self):
+        """The site as the ordinary distribution class over the evaluated predictor."""
+        eta = self.predictor.materialize()
+        if self.family == _lib.GLM_NORMAL:
+            return Normal(eta, self.aux[0])
+        if self.family == _lib.GLM_STUDENT_T:
+            return StudentT(self.aux[0], eta, self.aux[1])
+        if self.family == _lib.GLM_POISSON_LOG:
+            return Poisson(eta.exp())
+        return Binomial(self.count, logits=eta)
+
+    def expand(self, batch_shape, _instance=None):
+        batch_shape = torch.Size(batch_shape)
+        if batch_shape == self.batch_shape:
+            return self
+        # a wider batch than the lazy form can express: materialise (unfused path)
+        return self.ordinary().expand(batch_shape)
+
+    def sample(self, sample_shape=torch.Size()):
+        with torch.no_grad():
+            return self.ordinary().expand(self.batch_shape).sample(sample_shape)
+
+    def log_prob(self, value):
+        return self.ordinary().log_prob(value)
+
+    def fused_log_prob_sum(self, value, scale=1.0, mask=None):
+        ll = self.fused_log_prob_batch(value, scale, mask)
+        return None if ll is None else ll.sum()
+
+    def fused_log_prob_batch(self, value, scale=1.0, mask=None):
+        """Per-particle / per-chain sums over the data plate: a tensor of the site's leading shape (one fused pass
+        over X for all of them); None when the kernel does not cover the call (then log_prob evaluates)."""
+        lz = self.predictor
+        N, D = lz.X.shape
+        if isinstance(scale, torch.Tensor) or not _maskable(mask):
+            return None
+        if not isinstance(value, torch.Tensor) or value.dim() != 1 or value.shape[0] != N:
+            return None
+        if lz.X.dtype != torch.float32 or D > 128 or not lz.X.is_contiguous():
+            return None
+        if mask is not None:
+            if mask.dim() != 1 or mask.shape[0] != N:
+                return None
+            mask = mask.contiguous()
+        lead = self.batch_shape[:-1]
+        P = 1
+        for n in lead:
+            P *= n
+        w = lz.w
+        w2 = (w.expand(lead + (1, D)) if w.dim() > 1 else w.expand(lead + (D,))).reshape(P, D).contiguous()
+        b1 = None
+        if lz.b is not None:
+            b1 = (lz.b if lz.b.dim() > 0 else lz.b.reshape(1)).expand(lead + (1,)).reshape(P).contiguous()
+        aux = None
+        if self.aux:
+            aux = torch.stack([(a if a.dim() > 0 else a.reshape(1)).expand(lead + (1,)).reshape(P)
+                               for a in self.aux], dim=-1)
+        count = self.count
+        if isinstance(count, torch.Tensor):
+            # (a 0-dim device count becomes a per-row one: reading it on the host would be a synchronisation at
+            #  every scoring call, and is not permitted while a step is being captured)
+            count = count.to(torch.float32).expand(N).contiguous()
+        y = value if value.dtype == torch.float32 else value.to(torch.float32)
+        ll = fused.glm_family_ll(self.family, lz.X, y.contiguous(), w2, b1, aux, count, mask, scale)
+        return ll.reshape(lead)
+
+
+_ORDINARY = {_lib.GLM_NORMAL: lambda: torch.distributions.Normal,
+             _lib.GLM_STUDENT_T: lambda: torch.distributions.StudentT,
+             _lib.GLM_POISSON_LOG: lambda: torch.distributions.Poisson,
+             _lib.GLM_BINOMIAL_LOGITS: lambda: torch.distributions.Binomial}
 
 
 class Bernoulli(_FusedElementwise, torch.distributions.Bernoulli, TorchDistributionMixin):

@@ -1056,6 +1056,46 @@ def glm_bernoulli_ll(X, y, w, b=None, mask=None, scale=1.0):
     return _GlmBernoulliSum.invoke(X, y, w, b, mask, float(scale))
 
 
+@_dispatcher_op("glm_family_ll")
+class _GlmFamilySum(torch.autograd.Function):
+    """Per particle, scale * sum_n mask_n t(y_n, w_p.x_n + b_p; aux_p) -- the data-dependent part of a plated
+    Normal / StudentT / Poisson / Binomial regression site -- and the number of unmasked rows: forward and backward
+    of the whole observed site from ONE pass over X (pa_glm_family_fwd_bwd)."""
+
+    @staticmethod
+    def forward(ctx, family, X, y, w, b, aux, count, mask, scale):
+        s, gw, gb, gaux, cnt = kernels.glm_family_fwd_bwd(family, X, y, w, b, aux, count, mask, scale)
+        ctx.save_for_backward(gw, gb, gaux)
+        ctx.has_b = b is not None
+        ctx.mark_non_differentiable(cnt)
+        return s, cnt
+
+    @staticmethod
+    def backward(ctx, g, _g_cnt=None):
+        gw, gb, gaux = ctx.saved_tensors
+        dw, db = kernels.glm_chain(g, gw, gb, ctx.needs_input_grad[3],
+                                   ctx.has_b and ctx.needs_input_grad[4])
+        da = g.reshape(-1, 1) * gaux if (gaux is not None and ctx.needs_input_grad[5]) else None
+        return None, None, None, dw, db, da, None, None, None
+
+
+def glm_family_ll(family, X, y, w, b=None, aux=None, count=None, mask=None, scale=1.0):
+    """Per-particle log-likelihood ll[P] of a plated regression site (differentiable w.r.t. w[P,D], b[P] and
+    aux[P,A]): the kernel's data-dependent sum plus scale * (unmasked rows) * c(aux_p), the normaliser that depends
+    on the particle only, in closed form on [P] tensors."""
+    import math
+    from .. import _lib
+    s, cnt = _GlmFamilySum.invoke(family, X, y, w, b, aux, count, mask, float(scale))
+    if family == _lib.GLM_NORMAL:
+        c = -aux[:, 0].log() - 0.5 * math.log(2.0 * math.pi)
+    elif family == _lib.GLM_STUDENT_T:
+        nu, sigma = aux[:, 0], aux[:, 1]
+        c = torch.lgamma(0.5 * (nu + 1.0)) - torch.lgamma(0.5 * nu) - 0.5 * (nu * math.pi).log() - sigma.log()
+    else:
+        return s
+    return s + (float(scale) * cnt.to(s.dtype)) * c
+
+
 @_dispatcher_op("glm_bernoulli_grouped_ll")
 class _GlmBernoulliGroupedSum(torch.autograd.Function):
     """Hierarchical GLM site: ll[P] and d ll / d (w[P,G,D], b[P]) from one pass over the

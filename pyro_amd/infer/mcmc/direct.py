@@ -215,7 +215,9 @@ def _recognise(pe_maker, layout, transforms, init_params, C):
             seen.add(name)
         else:                                                         # an observed site: the GLM, once
             lz = getattr(fn, "lazy", None)
-            if glm is not None or lz is None or type(lz).__name__ != "LinearLogits" or not site["is_observed"]:
+            # (the Bernoulli site alone: the other regression families keep the generic potential)
+            if glm is not None or lz is None or type(lz).__name__ != "LinearLogits" or not site["is_observed"] \
+                    or type(fn).__name__ != "_BernoulliLinear":
                 return None
             X, y = lz.X, site["value"]
             if not (X.is_cuda and X.dtype == torch.float32 and X.is_contiguous() and y.dim() == 1

@@ -1554,6 +1554,55 @@ def glm_bernoulli_fwd_bwd(X, y, w, b, mask, scale):
     return ll, gw, gb
 
 
+def glm_family_fwd_bwd(family, X, y, w, b, aux, count, mask, scale, _max_blocks=0):
+    """The plated regression site of ``family`` (_lib.GLM_NORMAL / GLM_STUDENT_T / GLM_POISSON_LOG /
+    GLM_BINOMIAL_LOGITS) in one pass over X: X[N,D], y[N], w[P,D], b[P] or None, aux[P,A] (sigma | nu, sigma |
+    None), count: [N] tensor, a number or None (Binomial only), mask[N] bool or None ->
+    (s[P], gw[P,D], gb[P], gaux[P,A] or None, cnt float64 [1]).  ``s`` is the data-dependent part of the summed log
+    density (pa_glm_family_fwd_bwd); ``_max_blocks`` caps the grid (tests)."""
+    _require_gpu(X, y, w, b, aux, mask, count if isinstance(count, torch.Tensor) else None)
+    if X.dtype != torch.float32:
+        raise Unsupported("pyro_amd: fused GLM kernel is float32 only")
+    N, D = X.shape
+    P = w.shape[0]
+    A = _lib.GLM_AUX_COLUMNS[family]
+    assert X.is_contiguous() and y.is_contiguous() and w.is_contiguous()
+    assert y.shape == (N,) and w.shape == (P, D)
+    assert y.dtype == torch.float32 and w.dtype == torch.float32
+    if b is not None:
+        assert b.is_contiguous() and b.shape == (P,) and b.dtype == torch.float32
+    if mask is not None:
+        assert mask.is_contiguous() and mask.shape == (N,) and mask.dtype in (torch.bool,
+                                                                             torch.uint8)
+    if A:
+        assert aux is not None and aux.is_contiguous() and aux.shape == (P, A) and aux.dtype == torch.float32
+    else:
+        assert aux is None
+    count_t, count_s = None, 0.0
+    if family == _lib.GLM_BINOMIAL_LOGITS:
+        if isinstance(count, torch.Tensor):
+            assert count.is_contiguous() and count.shape == (N,) and count.dtype == torch.float32
+            count_t = count
+        else:
+            count_s = float(count)
+    else:
+        assert count is None
+    lib = _lib.load()
+    nbytes = lib.pa_glm_family_workspace(family, N, D, P, int(_max_blocks))
+    if nbytes == 0:
+        raise Unsupported("pyro_amd: fused GLM family kernel does not support N=%d D=%d P=%d" % (N, D, P))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=X.device)
+    s = torch.empty((P,), dtype=X.dtype, device=X.device)
+    gw = torch.empty((P, D), dtype=X.dtype, device=X.device)
+    gb = torch.empty((P,), dtype=X.dtype, device=X.device)
+    gaux = torch.empty((P, A), dtype=X.dtype, device=X.device) if A else None
+    cnt = torch.empty((1,), dtype=torch.float64, device=X.device)
+    check(lib.pa_glm_family_fwd_bwd(family, _ptr(X), _ptr(y), _ptr(w), _ptr(b), _ptr(aux), _ptr(count_t), count_s,
+                                    _ptr(mask), float(scale), N, D, P, int(_max_blocks), _ptr(s), _ptr(gw),
+                                    _ptr(gb), _ptr(gaux), _ptr(cnt), _ptr(ws), nbytes, _stream()))
+    return s, gw, gb, gaux, cnt
+
+
 def glm_chain(g, gw, gb, need_w=True, need_b=True):
     """(g[:, None...] * gw, g * gb) in one launch: the backward of the fused GLM site."""
     _require_gpu(g, gw, gb)

@@ -16,6 +16,12 @@ DeferredMatmul supports exactly what such model text does next (``squeeze``, ``+
 queries); ``Bernoulli(logits=...)`` turns it into the fused site; ANY other use (a torch function,
 an attribute, arithmetic beyond the bias) materialises the product -- then the model runs exactly
 as written, on the unfused route.  Every other operation on a latent returns plain tensors.
+
+The other plated regressions reach their fused site (distributions/families.py::_LinearPredictor) the same
+way: ``Normal(d, sigma)``, ``StudentT(nu, d, sigma)`` and ``Binomial(n, logits=d)`` take the deferred product
+as it is, and count regression writes ``Poisson(torch.exp(d))`` -- so ``d.exp()`` / ``torch.exp(d)`` return a
+DeferredMatmul that carries the link ``"exp"`` and nothing else: every further operation on a linked object
+materialises ``exp(product)``, and ``Bernoulli(logits=torch.exp(...))`` sees no linear logits.
 """
 import torch
 
@@ -137,8 +143,8 @@ def as_latent(value):
 class DeferredMatmul:
     """``w @ X.t()`` (or ``X @ w``) not yet evaluated.  ``w``: [D] or [..., 1, D]."""
 
-    def __init__(self, X, w, squeezed=False, bias=None):
-        self.X, self.w, self.squeezed, self.bias = X, w, squeezed, bias
+    def __init__(self, X, w, squeezed=False, bias=None, link=None):
+        self.X, self.w, self.squeezed, self.bias, self.link = X, w, squeezed, bias, link
         N = X.shape[0]
         if w.dim() == 1:
             shape = (N,)
@@ -164,14 +170,14 @@ class DeferredMatmul:
 
     def squeeze(self, d=None):
         if self.bias is None and not self.squeezed and self.w.dim() > 1 and d is not None \
-                and d % len(self.shape) == len(self.shape) - 2:
+                and self.link is None and d % len(self.shape) == len(self.shape) - 2:
             return DeferredMatmul(self.X, self.w, True, None)
         return self.materialize().squeeze() if d is None else self.materialize().squeeze(d)
 
     def _with_bias(self, other):
         other = _plain(other) if isinstance(other, torch.Tensor) else other
         flat = self.w.dim() == 1 or self.squeezed
-        if self.bias is None and flat:
+        if self.bias is None and flat and self.link is None:
             if isinstance(other, (int, float)):
                 return DeferredMatmul(self.X, self.w, self.squeezed,
                                       torch.full((), float(other), dtype=self.dtype, device=self.device))
@@ -187,12 +193,29 @@ class DeferredMatmul:
     def as_linear_logits(self):
         """The fused site's lazy operand, or None when this shape is not the plated GLM."""
         from ..distributions.families import LinearLogits
-        if self.w.dim() > 1 and not self.squeezed:
+        if (self.w.dim() > 1 and not self.squeezed) or self.link is not None:
             return None
         try:
             return LinearLogits(self.X, self.w, self.bias)
         except ValueError:
             return None
+
+    def as_linear_predictor(self):
+        """(the lazy linear predictor, its link: "identity" or "exp"), or None when this shape is not a plated
+        regression."""
+        from ..distributions.families import LinearLogits
+        if self.w.dim() > 1 and not self.squeezed:
+            return None
+        try:
+            return LinearLogits(self.X, self.w, self.bias), (self.link or "identity")
+        except ValueError:
+            return None
+
+    def exp(self):
+        """The log link of count regression: stays deferred once; anything further evaluates."""
+        if self.link is None and ENABLED["on"]:
+            return DeferredMatmul(self.X, self.w, self.squeezed, self.bias, "exp")
+        return self.materialize().exp()
 
     # ---- everything else: evaluate, then behave as the tensor ------------------------------------
     def materialize(self):
@@ -201,6 +224,8 @@ class DeferredMatmul:
             out = out.squeeze(-2)
         if self.bias is not None:
             out = out + self.bias
+        if self.link == "exp":
+            out = out.exp()
         return out
 
     @classmethod
@@ -209,6 +234,9 @@ class DeferredMatmul:
             d, o = (args[0], args[1]) if isinstance(args[0], DeferredMatmul) else (args[1], args[0])
             if not isinstance(o, DeferredMatmul):
                 return d._with_bias(o)                                      # b + logits
+        if len(args) == 1 and not kwargs and getattr(func, "__name__", "") == "exp" \
+                and isinstance(args[0], DeferredMatmul):
+            return args[0].exp()                                            # torch.exp(logits)
 
         def ev(x):
             if isinstance(x, DeferredMatmul):
