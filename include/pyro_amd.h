@@ -1120,6 +1120,38 @@ int pa_forecast_scores(int dtype, const void* pred, const void* truth, int64_t S
 int pa_time_transform(int dtype, int op, const void* x, void* y, int64_t outer, int64_t n, int64_t inner,
                       pa_stream_t stream);
 
+/* ---- csrc/gp_kernel.hip: stationary covariance matrices of Gaussian-process models, by direct differences -------
+ * Replaces pyro/contrib/gp/kernels/isotropic.py (r2 = X2 - 2 X Z^T + Z2, clamped, then four to eight element-wise
+ * torch passes over [N, M], and autograd's dozen launches for the backward):
+ *   K[i, j] = variance * f(r2_ij),  r2_ij = sum_k ((x_ik - z_jk) / l_k)^2,  r = sqrt(r2 + 1e-12)
+ *   PA_GP_RBF exp(-r2 / 2)   PA_GP_RATIONAL_QUADRATIC (1 + r2 / (2 alpha))^-alpha   PA_GP_EXPONENTIAL exp(-r)
+ *   PA_GP_MATERN32 (1 + sqrt3 r) exp(-sqrt3 r)   PA_GP_MATERN52 (1 + sqrt5 r + 5/3 r2) exp(-sqrt5 r)
+ * x [N, D], z [M, D] contiguous (z = NULL: z = x, M = N), lengthscale [n_ls] with n_ls = 1 or D, variance [1], alpha [1]
+ * (RationalQuadratic only, else NULL), all of one dtype (f32 / f64) and all DEVICE pointers: no parameter is read on
+ * the host.  1 <= D <= 64, else PA_ERR_UNSUPPORTED.
+ * pa_gp_kernel_fwd: ONE launch; K [N, M] contiguous is written once.  N = 0 or M = 0: PA_OK without a launch.
+ * pa_gp_kernel_bwd: G [N, M] contiguous, the gradient with respect to K.  Outputs that are NULL are not computed:
+ * gx [N, D], gz [M, D] (needs z; with z = NULL gx takes both roles), g_lengthscale [n_ls], g_variance [1], g_alpha [1].
+ * r2 and f are recomputed from the inputs: nothing of the forward is needed, K may have been overwritten.  One pass
+ * over G per side that wants a gradient (two reads in one pass for z = NULL), partial records in ``workspace``
+ * (pa_gp_kernel_bwd_workspace bytes for the same shape and flags; checked against the plan's records), summed in a
+ * fixed order in float64: no atomics, bit-reproducible.  forced_splits > 0 fixes the number of column splits (tests).
+ * N and M must both be positive when an output is asked for. */
+#define PA_GP_RBF 0
+#define PA_GP_RATIONAL_QUADRATIC 1
+#define PA_GP_EXPONENTIAL 2
+#define PA_GP_MATERN32 3
+#define PA_GP_MATERN52 4
+int pa_gp_kernel_fwd(int dtype, int family, const void* x, const void* z, const void* lengthscale, int n_ls,
+                     const void* variance, const void* alpha, void* K, int64_t N, int64_t M, int64_t D,
+                     pa_stream_t stream);
+size_t pa_gp_kernel_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int want_gx, int want_gz,
+                                  int forced_splits);
+int pa_gp_kernel_bwd(int dtype, int family, const void* x, const void* z, const void* lengthscale, int n_ls,
+                     const void* variance, const void* alpha, const void* G, int64_t N, int64_t M, int64_t D, void* gx,
+                     void* gz, void* g_lengthscale, void* g_variance, void* g_alpha, int forced_splits, void* workspace,
+                     size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -366,6 +366,12 @@ _SIGNATURES = {
                            + [c_void_p] * 4),                                                     # mean median crps, stream
     "pa_time_transform": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,     # dtype op x y outer n inner
                                   c_void_p]),                                                       # stream
+    "pa_gp_kernel_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,   # .. x z ls n_ls var alpha
+                                 c_void_p, c_int64, c_int64, c_int64, c_void_p]),                        # K N M D stream
+    "pa_gp_kernel_bwd_workspace": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_kernel_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int64, c_int64, c_int64]                                    # G N M D
+                         + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),                      # grads, splits ws stream
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

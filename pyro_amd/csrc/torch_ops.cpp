@@ -670,6 +670,78 @@ at::Tensor time_transform(const at::Tensor& x, int64_t op, int64_t dim) {
   return y;
 }
 
+// the covariance matrix of a stationary Gaussian-process kernel by direct differences, one launch
+// (pyro/contrib/gp/kernels/isotropic.py): family 0 RBF, 1 RationalQuadratic (alpha = scale_mixture), 2 Exponential,
+// 3 Matern32, 4 Matern52; x [N, D], z [M, D] or none for z = x -> K [N, M].  Parameters stay on the device.
+struct GpArgs {
+  int dt;
+  int64_t N, M, D;
+  const void *z, *alpha;
+};
+GpArgs gp_args(const char* who, const at::Tensor& x, const std::optional<at::Tensor>& z, const at::Tensor& lengthscale,
+               const at::Tensor& variance, const std::optional<at::Tensor>& alpha, int64_t family) {
+  GpArgs a;
+  a.dt = dtype_of(x, who);
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(1) >= 1 && x.size(1) <= 64 && family >= 0 && family <= 4,
+              "pyro_amd::", who, ": x [N, D] contiguous, 1 <= D <= 64, family in 0..4");
+  a.N = x.size(0), a.D = x.size(1), a.M = a.N, a.z = nullptr, a.alpha = nullptr;
+  auto same = [&](const at::Tensor& t) { return t.is_cuda() && t.is_contiguous() && t.scalar_type() == x.scalar_type(); };
+  if (z.has_value() && z->defined()) {
+    TORCH_CHECK(same(*z) && z->dim() == 2 && z->size(1) == a.D, "pyro_amd::", who, ": z [M, D] contiguous, of x's dtype");
+    a.M = z->size(0), a.z = z->data_ptr();
+  }
+  TORCH_CHECK(same(lengthscale) && same(variance) && (lengthscale.numel() == 1 || lengthscale.numel() == a.D) &&
+                  variance.numel() == 1,
+              "pyro_amd::", who, ": lengthscale of 1 or D elements, variance of 1, of x's dtype");
+  const bool has_alpha = alpha.has_value() && alpha->defined();
+  TORCH_CHECK(has_alpha == (family == 1) && (!has_alpha || (same(*alpha) && alpha->numel() == 1)), "pyro_amd::", who,
+              ": alpha (one element) with family 1 and only with it");
+  if (has_alpha) a.alpha = alpha->data_ptr();
+  return a;
+}
+
+at::Tensor gp_kernel(const at::Tensor& x, const std::optional<at::Tensor>& z, const at::Tensor& lengthscale,
+                     const at::Tensor& variance, const std::optional<at::Tensor>& alpha, int64_t family) {
+  const GpArgs a = gp_args("gp_kernel", x, z, lengthscale, variance, alpha, family);
+  at::Tensor K = at::empty({a.N, a.M}, x.options());
+  if (a.N == 0 || a.M == 0) return K;
+  check(pa_gp_kernel_fwd(a.dt, (int)family, x.data_ptr(), a.z, lengthscale.data_ptr(), (int)lengthscale.numel(),
+                         variance.data_ptr(), a.alpha, K.data_ptr(), a.N, a.M, a.D, current_stream()),
+        "gp_kernel");
+  return K;
+}
+
+// its gradients given G = dL/dK [N, M] contiguous: (gx, gz, g_lengthscale, g_variance, g_alpha), an empty tensor where
+// want_* is false (gz also without a z, g_alpha also outside family 1); K is not an input -- everything is recomputed
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gp_kernel_bwd(
+    const at::Tensor& x, const std::optional<at::Tensor>& z, const at::Tensor& lengthscale, const at::Tensor& variance,
+    const std::optional<at::Tensor>& alpha, const at::Tensor& G, int64_t family, bool want_x, bool want_z,
+    bool want_lengthscale, bool want_variance, bool want_alpha, int64_t forced_splits) {
+  const GpArgs a = gp_args("gp_kernel_bwd", x, z, lengthscale, variance, alpha, family);
+  TORCH_CHECK(G.is_cuda() && G.is_contiguous() && G.scalar_type() == x.scalar_type() && G.dim() == 2 && G.size(0) == a.N &&
+                  G.size(1) == a.M && forced_splits >= 0,
+              "pyro_amd::gp_kernel_bwd: G [N, M] contiguous, of x's dtype");
+  want_z = want_z && a.z != nullptr;
+  want_alpha = want_alpha && a.alpha != nullptr;
+  const bool none = a.N == 0 || a.M == 0;      // (no launch: zeros; else the finalize kernel writes every wanted entry)
+  auto out = [&](bool want, const at::Tensor& like) {
+    return want ? (none ? at::zeros_like(like) : at::empty_like(like)) : at::empty({0}, x.options());
+  };
+  at::Tensor gx = out(want_x, x), gz = out(want_z, want_z ? *z : x), gl = out(want_lengthscale, lengthscale),
+             gv = out(want_variance, variance), ga = out(want_alpha, want_alpha ? *alpha : variance);
+  if (a.N == 0 || a.M == 0 || !(want_x || want_z || want_lengthscale || want_variance || want_alpha))
+    return {gx, gz, gl, gv, ga};
+  const size_t ws_bytes = pa_gp_kernel_bwd_workspace(a.N, a.M, a.D, a.z == nullptr, want_x, want_z, (int)forced_splits);
+  at::Tensor ws = at::empty({(int64_t)((ws_bytes < 8 ? 8 : ws_bytes) + 7) / 8}, x.options().dtype(at::kDouble));
+  auto ptr = [](bool want, at::Tensor& t) -> void* { return want ? t.data_ptr() : nullptr; };
+  check(pa_gp_kernel_bwd(a.dt, (int)family, x.data_ptr(), a.z, lengthscale.data_ptr(), (int)lengthscale.numel(),
+                         variance.data_ptr(), a.alpha, G.data_ptr(), a.N, a.M, a.D, ptr(want_x, gx), ptr(want_z, gz),
+                         ptr(want_lengthscale, gl), ptr(want_variance, gv), ptr(want_alpha, ga), (int)forced_splits,
+                         ws.data_ptr(), (size_t)ws.numel() * 8, current_stream()),
+        "gp_kernel_bwd");
+  return {gx, gz, gl, gv, ga};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -861,6 +933,10 @@ TORCH_LIBRARY(pyro_amd, m) {
         "(Tensor y, Tensor[] states)");
   m.def("forecast_scores(Tensor pred, Tensor truth) -> (Tensor mean, Tensor median, Tensor crps)");
   m.def("time_transform(Tensor x, int op, int dim) -> Tensor");
+  m.def("gp_kernel(Tensor x, Tensor? z, Tensor lengthscale, Tensor variance, Tensor? alpha, int family) -> Tensor");
+  m.def("gp_kernel_bwd(Tensor x, Tensor? z, Tensor lengthscale, Tensor variance, Tensor? alpha, Tensor G, int family, "
+        "bool want_x, bool want_z, bool want_lengthscale, bool want_variance, bool want_alpha, int forced_splits) -> "
+        "(Tensor gx, Tensor gz, Tensor g_lengthscale, Tensor g_variance, Tensor g_alpha)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -897,6 +973,8 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("linear_hmm_draw", &linear_hmm_draw);
   m.impl("forecast_scores", &forecast_scores);
   m.impl("time_transform", &time_transform);
+  m.impl("gp_kernel", &gp_kernel);
+  m.impl("gp_kernel_bwd", &gp_kernel_bwd);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

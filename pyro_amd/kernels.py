@@ -1128,6 +1128,80 @@ def time_transform(x, op, dim=-1):
     return y
 
 
+GP_FAMILIES = {"rbf": 0, "rational_quadratic": 1, "exponential": 2, "matern32": 3, "matern52": 4}
+GP_KERNEL_MAX_D = 64                      # (csrc/gp_kernel_plan.h GPK_MAX_D)
+
+
+def _gp_kernel_args(x, z, lengthscale, variance, alpha, family):
+    family = GP_FAMILIES.get(family, family)
+    assert family in (0, 1, 2, 3, 4), "gp_kernel: family is 0..4 or one of %s" % sorted(GP_FAMILIES)
+    _require_gpu(x, z, lengthscale, variance, alpha)
+    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_kernel: x [N, D], z [M, D]"
+    D = x.shape[1]
+    if not 1 <= D <= GP_KERNEL_MAX_D:
+        raise Unsupported("pyro_amd: gp_kernel: D=%d outside [1, %d]" % (D, GP_KERNEL_MAX_D))
+    for t in (z, lengthscale, variance, alpha):
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError("pyro_amd: gp_kernel: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    if lengthscale.numel() not in (1, D) or variance.numel() != 1 or (alpha is not None and alpha.numel() != 1):
+        raise ValueError("pyro_amd: gp_kernel: lengthscale has 1 or D elements, variance and scale_mixture 1")
+    if (family == 1) != (alpha is not None):
+        raise ValueError("pyro_amd: gp_kernel: scale_mixture goes with the RationalQuadratic family, and only with it")
+    x = x.contiguous()
+    z = None if z is None else z.contiguous()
+    return family, x, z, lengthscale.contiguous(), variance.contiguous(), None if alpha is None else alpha.contiguous()
+
+
+def gp_kernel_fwd(x, z, lengthscale, variance, alpha=None, family="rbf"):
+    """K [N, M] = variance * f(|x_i - z_j|^2 / l^2) of a stationary family (GP_FAMILIES) by direct differences, ONE launch
+    (pa_gp_kernel_fwd).  x [N, D], z [M, D] or None for z = x; lengthscale of 1 or D elements, variance and (for
+    "rational_quadratic") alpha of one: device tensors of x's dtype (f32 / f64), read by the kernel.  D over
+    GP_KERNEL_MAX_D raises Unsupported; an empty result makes no launch."""
+    family, x, z, lengthscale, variance, alpha = _gp_kernel_args(x, z, lengthscale, variance, alpha, family)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    K = x.new_empty((N, M))
+    if N == 0 or M == 0:
+        return K
+    check(_lib.load().pa_gp_kernel_fwd(_dtype(x), family, _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(),
+                                       _ptr(variance), _ptr(alpha), _ptr(K), N, M, D, _stream()))
+    return K
+
+
+def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(True, True, True, True, True),
+                  forced_splits=0):
+    """The gradients of gp_kernel_fwd's K given G = dL/dK [N, M]: (gx, gz, g_lengthscale, g_variance, g_alpha), ``None``
+    where ``want`` is false (gz also when z is None: gx then takes both roles; g_alpha also outside the
+    RationalQuadratic family).  r2 and f are recomputed from the inputs -- K itself is not an argument -- in one pass
+    over G per side that wants a gradient, then a fixed-order float64 finalize (pa_gp_kernel_bwd): bit-reproducible.
+    ``forced_splits`` > 0 fixes the number of column splits (tests)."""
+    family, x, z, lengthscale, variance, alpha = _gp_kernel_args(x, z, lengthscale, variance, alpha, family)
+    _require_gpu(G)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_kernel_bwd: G [N, M] of x's dtype"
+    G = G.contiguous()
+    want_gx, want_gz, want_ls, want_var, want_alpha = (bool(w) for w in want)
+    want_gz = want_gz and z is not None
+    want_alpha = want_alpha and alpha is not None
+    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
+    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
+    gx = make(x) if want_gx else None
+    gz = make(z) if want_gz else None
+    g_ls = make(lengthscale) if want_ls else None
+    g_var = make(variance) if want_var else None
+    g_alpha = make(alpha) if want_alpha else None
+    if empty or not (want_gx or want_gz or want_ls or want_var or want_alpha):
+        return gx, gz, g_ls, g_var, g_alpha
+    lib = _lib.load()
+    nbytes = lib.pa_gp_kernel_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    check(lib.pa_gp_kernel_bwd(_dtype(x), family, _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(variance),
+                               _ptr(alpha), _ptr(G), N, M, D, _ptr(gx), _ptr(gz), _ptr(g_ls), _ptr(g_var), _ptr(g_alpha),
+                               int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    return gx, gz, g_ls, g_var, g_alpha
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.

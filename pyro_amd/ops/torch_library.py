@@ -182,6 +182,20 @@ def _register():
     def _(x, op, dim):
         return torch.empty_like(x)
 
+    @lib.register_fake("pyro_amd::gp_kernel")
+    def _(x, z, lengthscale, variance, alpha, family):
+        return x.new_empty((x.shape[0], x.shape[0] if z is None else z.shape[0]))
+
+    @lib.register_fake("pyro_amd::gp_kernel_bwd")
+    def _(x, z, lengthscale, variance, alpha, G, family, want_x, want_z, want_lengthscale, want_variance, want_alpha,
+          forced_splits):
+        def out(want, like):
+            return torch.empty_like(like) if want else x.new_empty((0,))
+        want_z = want_z and z is not None
+        want_alpha = want_alpha and alpha is not None
+        return (out(want_x, x), out(want_z, z if want_z else x), out(want_lengthscale, lengthscale),
+                out(want_variance, variance), out(want_alpha, alpha if want_alpha else variance))
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -664,4 +678,5 @@ def registered_ops():
 TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample", "exp_site", "exp_site_bwd",
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
              "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw",
-             "gaussian_hmm_smooth", "gamma_gaussian_hmm", "linear_hmm_draw", "forecast_scores", "time_transform")
+             "gaussian_hmm_smooth", "gamma_gaussian_hmm", "linear_hmm_draw", "forecast_scores", "time_transform",
+             "gp_kernel", "gp_kernel_bwd")
