@@ -179,6 +179,15 @@ class _CapturedStep:
                 torch.cuda.current_stream().synchronize()
                 if int(seq[0]) == last:
                     raise RuntimeError("pyro_amd: the captured step did not publish its loss")
+        if ack is not None and int(ack[0]) == g.next:
+            # the loss was there before this loop looked at the gate once (the host was held up in the
+            # launch of the replay it armed for the next step): the released replay had given itself up
+            # all the same, and the one just armed found its number released and ran as this step --
+            # nothing waits behind the gate any more
+            gave_up = True
+            self.armed = False
+            self.arm_backoff = self.arm_penalty
+            self.arm_penalty = min(self.arm_penalty * 2, 1024)
         self._seq = int(seq[0])
         if released_armed and not gave_up and self.arm_penalty > 1:
             self.arm_penalty >>= 1          # an armed replay that ran: the back-off decays again

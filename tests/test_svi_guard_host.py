@@ -22,6 +22,30 @@ def test_prearm_is_opt_in():
         assert s.prearm is want, kw
 
 
+def test_a_replay_given_up_is_noticed_when_its_stand_in_has_already_published():
+    """The released replay gave itself up (ack == its number) and the replay armed behind it ran as this
+    step and published BEFORE read_loss looked once: nothing waits behind the gate any more, so the entry
+    may not go on believing that a replay is armed (the step after would release a replay that is not
+    there).  Without a give-up the same call leaves the armed replay armed."""
+    import types
+
+    import numpy as np
+
+    def entry_after(ack):
+        mailbox = (torch.zeros(1, dtype=torch.float64), torch.zeros(1, dtype=torch.int64))
+        e = svi_mod._CapturedStep(None, None, None, mailbox=mailbox)
+        e.gate = types.SimpleNamespace(go_np=np.full(1, 2), ack_np=np.full(1, ack), next=2)
+        e.armed = True                      # (the replay enqueued for the step after this one)
+        mailbox[0][0], mailbox[1][0] = 1.5, 7          # ... has published as this step
+        assert e.read_loss(released_armed=True) == 1.5 and e.gate.next == 3
+        return e
+
+    e = entry_after(ack=2)
+    assert not e.armed and e.arm_backoff == 1 and e.arm_penalty == 2
+    e = entry_after(ack=1)                  # (an earlier give-up, long dealt with)
+    assert e.armed and e.arm_backoff == 0 and e.arm_penalty == 1
+
+
 BETA = 0.5
 
 
