@@ -1152,6 +1152,27 @@ int pa_gp_kernel_bwd(int dtype, int family, const void* x, const void* z, const 
                      void* gz, void* g_lengthscale, void* g_variance, void* g_alpha, int forced_splits, void* workspace,
                      size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_sgpr.hip: the statistics of a sparse GP regression (DTC / VFE), streamed: Kuf [M, N] is never formed --
+ * With Kuf[i, n] = k(xu_i, x_n) of the families above (same r2: direct differences, float64 up to the exponential):
+ *   pa_gp_sgpr_fwd:  A [M, M] = Kuf Kuf^T (both triangles written, exactly symmetric),  b [M, Q] = Kuf r
+ *   pa_gp_sgpr_bwd:  given gA [M, M] (any, not assumed symmetric) and gb [M, Q], with G = (gA + gA^T) Kuf + gb r^T
+ *                    formed block by block in registers: gx [N, D], gxu [M, D], g_lengthscale [n_ls], g_variance [1],
+ *                    g_alpha [1] as pa_gp_kernel_bwd would give for G, and gr [N, Q] = Kuf^T gb.  NULL: not computed.
+ * x [N, D], xu [M, D], r [N, Q] contiguous, all DEVICE pointers of one dtype.  f32 runs the products on
+ * v_mfma_f32_32x32x2_f32, f64 on the VALU.  1 <= D <= 64, 1 <= Q <= 16, M <= 512 (f32) / 256 (f64), else
+ * PA_ERR_UNSUPPORTED.  Partial records in ``workspace`` (pa_gp_sgpr_workspace bytes for the same shape, direction and
+ * flags; checked against the plan), summed in a fixed order in float64: no atomics, bit-reproducible.
+ * forced_splits > 0 fixes the number of splits of N (tests).  N = 0 or M = 0: PA_OK without a launch. */
+size_t pa_gp_sgpr_workspace(int dtype, int64_t N, int64_t M, int64_t D, int64_t Q, int backward, int want_gx,
+                            int want_gxu, int forced_splits);
+int pa_gp_sgpr_fwd(int dtype, int family, const void* x, const void* xu, const void* r, const void* lengthscale, int n_ls,
+                   const void* variance, const void* alpha, void* A, void* b, int64_t N, int64_t M, int64_t D, int64_t Q,
+                   int forced_splits, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+int pa_gp_sgpr_bwd(int dtype, int family, const void* x, const void* xu, const void* r, const void* lengthscale, int n_ls,
+                   const void* variance, const void* alpha, const void* gA, const void* gb, int64_t N, int64_t M, int64_t D,
+                   int64_t Q, void* gx, void* gxu, void* g_lengthscale, void* g_variance, void* g_alpha, void* gr,
+                   int forced_splits, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

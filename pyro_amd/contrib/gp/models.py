@@ -5,7 +5,14 @@ A model closes over its data: ``model()`` and ``guide()`` take no arguments, so 
 ``util.train``).  Covariance matrices come from ``self.kernel``; on the device the stationary families form them in one
 launch (``kernels.FUSED_GP_KERNEL``).  Noise and jitter are added to the diagonal of the matrix IN PLACE, as the
 reference does; the fused kernel's backward recomputes what it needs from the inputs, so that is allowed.
+
+``SparseGPRegression`` with DTC or VFE has a STREAMED route (``FUSED_SGPR``): the data enter the loss only through
+A = Kuf Kuf^T [M, M], b = Kuf r [M, Q], sum r^2 and sum_n k(x_n, x_n), and csrc/gp_sgpr.hip forms A and b (and their
+gradient) in one pass over X each way without Kuf [M, N] in memory; the rest is M x M algebra in torch
+(``streamed_log_prob``).
 """
+import math
+
 import torch
 from torch.distributions import constraints
 from torch.nn import Parameter
@@ -13,8 +20,12 @@ from torch.nn import Parameter
 from ... import distributions as dist
 from ... import primitives
 from ...nn.module import PyroParam, pyro_method
+from .kernels import Isotropy
 from .parameterized import Parameterized
 from .util import conditional
+
+FUSED_SGPR = True                 # SparseGPRegression, DTC / VFE: the statistics from pa_gp_sgpr_fwd / pa_gp_sgpr_bwd
+FUSED_SGPR_MIN_N = 1000000        # ... from this many data points on (README "Gaussian processes": the sweep)
 
 
 def _zero_mean_function(x):
@@ -26,6 +37,56 @@ def _add_to_diagonal(matrix, value):
     n = matrix.size(-1)
     matrix.view(-1)[::n + 1] += value
     return matrix
+
+
+class _StreamedStatistics(torch.autograd.Function):
+    """(A, b) = (Kuf Kuf^T, Kuf r) with Kuf[i, n] = k(xu_i, x_n), in one pass over x; the gradient is one more pass
+    (G = (gA + gA^T) Kuf + gb r^T exists only block by block inside the kernel).  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, xu, r, lengthscale, variance, alpha, family):
+        from ... import kernels
+        ctx.family = family
+        ctx.save_for_backward(x, xu, r, lengthscale, variance, alpha)
+        return kernels.gp_sgpr_fwd(x, xu, r, lengthscale.reshape(-1), variance.reshape(-1),
+                                   None if alpha is None else alpha.reshape(-1), family)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gA, gb):
+        from ... import kernels
+        x, xu, r, lengthscale, variance, alpha = ctx.saved_tensors
+        nx, nxu, nr, nl, nv, na = ctx.needs_input_grad[:6]
+        gx, gxu, gl, gv, ga, gr = kernels.gp_sgpr_bwd(
+            x, xu, r, lengthscale.reshape(-1), variance.reshape(-1), None if alpha is None else alpha.reshape(-1),
+            gA, gb, ctx.family, (nx, nxu, nl, nv, na, nr))
+        return (gx, gxu, gr, None if gl is None else gl.reshape(lengthscale.shape),
+                None if gv is None else gv.reshape(variance.shape),
+                None if ga is None else ga.reshape(alpha.shape), None)
+
+
+def streamed_factors(Luu, A, b, noise):
+    """From the statistics to the M x M quantities of the streamed route: C = Luu^-1 A Luu^-T, c = Luu^-1 b, and the
+    factor LB of I + C / noise.  (W D^-1 W^T = C / noise and W D^-1 r = c / noise for W = Luu^-1 Kuf, D = noise I.)"""
+    half = torch.linalg.solve_triangular(Luu, A, upper=False)
+    C = torch.linalg.solve_triangular(Luu, half.t(), upper=False)      # (A is symmetric)
+    c = torch.linalg.solve_triangular(Luu, b, upper=False)
+    LB = torch.linalg.cholesky(_add_to_diagonal((C / noise).contiguous(), 1))
+    return C, c, LB
+
+
+def streamed_log_prob(Luu, A, b, rr, kd, noise, N, approx):
+    """(log p(y), trace_term or None) of DTC / VFE from A = Kuf Kuf^T [M, M], b = Kuf r [M, Q], rr = sum r^2 and
+    kd = sum_n k(x_n, x_n):  with v = LB^-1 c,
+    log p(y) = -1/2 [Q (N log 2 pi + N log noise + 2 sum log diag LB) + rr / noise - |v|^2 / noise^2];
+    VFE's trace_term = clamp((kd - tr C) / noise, min=0)."""
+    Q = b.size(1)
+    C, c, LB = streamed_factors(Luu, A, b, noise)
+    v = torch.linalg.solve_triangular(LB, c, upper=False)
+    logdet = N * (math.log(2 * math.pi) + noise.log()) + 2 * LB.diagonal().log().sum()
+    log_prob = -0.5 * (Q * logdet + rr / noise - v.pow(2).sum() / noise ** 2)
+    trace_term = ((kd - C.diagonal().sum()) / noise).clamp(min=0) if approx == "VFE" else None
+    return log_prob, trace_term
 
 
 class GPModel(Parameterized):
@@ -172,10 +233,43 @@ class SparseGPRegression(GPModel):
         Kuf = self.kernel(self.Xu, self.X)
         return Luu, torch.linalg.solve_triangular(Luu, Kuf, upper=False)
 
+    def _streamed(self):
+        """(Luu, A, b, residual [N, Q], noise), all in FLOAT64, when the streamed route applies (module docstring), else
+        None.  Float32 models are cast up here and run the float64 kernels and float64 M x M algebra: A rounded (or
+        accumulated) in float32 is not a perturbation of Kuf, so Luu^-1 A Luu^-T would carry 2^-24 cond(Kuu) where the
+        dense route's W W^T does not (at cond = 2e3 the loss was off by 14 times the dense float32 route's error)."""
+        if not FUSED_SGPR or self.approx not in ("DTC", "VFE") or self.y is None or not isinstance(self.kernel, Isotropy):
+            return None
+        N, M = self.X.size(0), self.Xu.size(0)
+        if N < max(FUSED_SGPR_MIN_N, 1) or M < 1 or self.y.dtype != self.X.dtype or self.y.device != self.X.device:
+            return None
+        fused = self.kernel._fused(self.Xu, self.X)
+        if fused is None:
+            return None
+        from ... import kernels as hip
+        Q = self.y.numel() // N
+        if M > hip.GP_SGPR_MAX_M[torch.float64] or not 1 <= Q <= hip.GP_SGPR_MAX_Q or not self.noise.is_cuda:
+            return None
+        xu, x, lengthscale, variance, alpha = (None if t is None else t.double() for t in fused)
+        Kuu = self.kernel(self.Xu).contiguous().double()
+        Luu = torch.linalg.cholesky(_add_to_diagonal(Kuu, self.jitter))
+        residual = (self.y - self.mean_function(self.X)).reshape(-1, N).t().contiguous().double()
+        A, b = _StreamedStatistics.apply(x, xu, residual, lengthscale, variance, alpha, self.kernel._family)
+        return Luu, A, b, residual, self.noise.double()
+
     @pyro_method
     def model(self):
         self.set_mode("model")
         N = self.X.size(0)
+        streamed = self._streamed()
+        if streamed is not None:
+            Luu, A, b, residual, noise = streamed
+            kd = self.kernel(self.X, diag=True).double().sum()
+            log_prob, trace_term = streamed_log_prob(Luu, A, b, residual.pow(2).sum(), kd, noise, N, self.approx)
+            if trace_term is not None:
+                primitives.factor(self._pyro_get_fullname("trace_term"), (-trace_term / 2.0).to(self.X.dtype))
+            primitives.factor(self._pyro_get_fullname("y"), log_prob.to(self.X.dtype))
+            return self.y
         _, Wt = self._inducing()
         W = Wt.t()
         D = self.noise.expand(N)
@@ -205,15 +299,20 @@ class SparseGPRegression(GPModel):
         self._check_Xnew_shape(Xnew)
         self.set_mode("guide")
         N = self.X.size(0)
-        M = self.Xu.size(0)
-        Luu, W = self._inducing()
-        D = self.noise.expand(N)
-        if self.approx == "FITC":
-            D = D + self.kernel(self.X, diag=True) - W.pow(2).sum(dim=0)
-        W_Dinv = W / D
-        L = torch.linalg.cholesky(_add_to_diagonal(W_Dinv.matmul(W.t()).contiguous(), 1))
-        residual = (self.y - self.mean_function(self.X)).reshape(-1, N).t()
-        W_Dinv_y = W_Dinv.matmul(residual)
+        streamed = self._streamed()
+        if streamed is not None:          # W D^-1 W^T = C / noise and W D^-1 y = c / noise, from the statistics
+            Luu, A, b, _, noise = streamed
+            _, c, L = streamed_factors(Luu, A, b, noise)
+            Luu, L, W_Dinv_y = Luu.to(self.X.dtype), L.to(self.X.dtype), (c / noise).to(self.X.dtype)
+        else:
+            Luu, W = self._inducing()
+            D = self.noise.expand(N)
+            if self.approx == "FITC":
+                D = D + self.kernel(self.X, diag=True) - W.pow(2).sum(dim=0)
+            W_Dinv = W / D
+            L = torch.linalg.cholesky(_add_to_diagonal(W_Dinv.matmul(W.t()).contiguous(), 1))
+            residual = (self.y - self.mean_function(self.X)).reshape(-1, N).t()
+            W_Dinv_y = W_Dinv.matmul(residual)
         n_out = W_Dinv_y.size(1)
         Ws = torch.linalg.solve_triangular(Luu, self.kernel(self.Xu, Xnew), upper=False)
         solved = torch.linalg.solve_triangular(L, torch.cat((W_Dinv_y, Ws), dim=1), upper=False)

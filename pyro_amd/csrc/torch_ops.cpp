@@ -742,6 +742,65 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gp_kernel
   return {gx, gz, gl, gv, ga};
 }
 
+// the statistics of a sparse GP regression streamed over the data (csrc/gp_sgpr.hip): A [M, M] = Kuf Kuf^T and
+// b [M, Q] = Kuf r with Kuf[i, n] = k(xu_i, x_n), Kuf itself never in memory
+static void gp_sgpr_check(const char* who, const GpArgs& a, const at::Tensor& x, const at::Tensor& r) {
+  TORCH_CHECK(a.z != nullptr && r.is_cuda() && r.is_contiguous() && r.scalar_type() == x.scalar_type() && r.dim() == 2 &&
+                  r.size(0) == a.N && r.size(1) >= 1 && r.size(1) <= 16 && a.M <= (a.dt == PA_F32 ? 512 : 256),
+              "pyro_amd::", who, ": xu [M, D], r [N, Q] contiguous of x's dtype, 1 <= Q <= 16, M <= 512 (f32) / 256 (f64)");
+}
+
+std::tuple<at::Tensor, at::Tensor> gp_sgpr(const at::Tensor& x, const at::Tensor& xu, const at::Tensor& r,
+                                           const at::Tensor& lengthscale, const at::Tensor& variance,
+                                           const std::optional<at::Tensor>& alpha, int64_t family, int64_t forced_splits) {
+  const GpArgs a = gp_args("gp_sgpr", x, xu, lengthscale, variance, alpha, family);
+  gp_sgpr_check("gp_sgpr", a, x, r);
+  const int64_t Q = r.size(1);
+  if (a.N == 0 || a.M == 0) return {at::zeros({a.M, a.M}, x.options()), at::zeros({a.M, Q}, x.options())};
+  at::Tensor A = at::empty({a.M, a.M}, x.options()), b = at::empty({a.M, Q}, x.options());
+  const size_t ws_bytes = pa_gp_sgpr_workspace(a.dt, a.N, a.M, a.D, Q, 0, 0, 0, (int)forced_splits);
+  at::Tensor ws = at::empty({(int64_t)((ws_bytes < 8 ? 8 : ws_bytes) + 7) / 8}, x.options().dtype(at::kDouble));
+  check(pa_gp_sgpr_fwd(a.dt, (int)family, x.data_ptr(), a.z, r.data_ptr(), lengthscale.data_ptr(), (int)lengthscale.numel(),
+                       variance.data_ptr(), a.alpha, A.data_ptr(), b.data_ptr(), a.N, a.M, a.D, Q, (int)forced_splits,
+                       ws.data_ptr(), (size_t)ws.numel() * 8, current_stream()),
+        "gp_sgpr");
+  return {A, b};
+}
+
+// its gradients given gA [M, M] and gb [M, Q]: (gx, gxu, g_lengthscale, g_variance, g_alpha, gr), an empty tensor where
+// want_* is false (g_alpha also outside family 1)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gp_sgpr_bwd(
+    const at::Tensor& x, const at::Tensor& xu, const at::Tensor& r, const at::Tensor& lengthscale,
+    const at::Tensor& variance, const std::optional<at::Tensor>& alpha, const at::Tensor& gA, const at::Tensor& gb,
+    int64_t family, bool want_x, bool want_xu, bool want_lengthscale, bool want_variance, bool want_alpha, bool want_r,
+    int64_t forced_splits) {
+  const GpArgs a = gp_args("gp_sgpr_bwd", x, xu, lengthscale, variance, alpha, family);
+  gp_sgpr_check("gp_sgpr_bwd", a, x, r);
+  const int64_t Q = r.size(1);
+  auto same = [&](const at::Tensor& t) { return t.is_cuda() && t.is_contiguous() && t.scalar_type() == x.scalar_type(); };
+  TORCH_CHECK(same(gA) && same(gb) && gA.dim() == 2 && gA.size(0) == a.M && gA.size(1) == a.M && gb.dim() == 2 &&
+                  gb.size(0) == a.M && gb.size(1) == Q && forced_splits >= 0,
+              "pyro_amd::gp_sgpr_bwd: gA [M, M], gb [M, Q] contiguous, of x's dtype");
+  want_alpha = want_alpha && a.alpha != nullptr;
+  const bool none = a.N == 0 || a.M == 0;
+  auto out = [&](bool want, const at::Tensor& like) {
+    return want ? (none ? at::zeros_like(like) : at::empty_like(like)) : at::empty({0}, x.options());
+  };
+  at::Tensor gx = out(want_x, x), gxu = out(want_xu, xu), gl = out(want_lengthscale, lengthscale),
+             gv = out(want_variance, variance), ga = out(want_alpha, want_alpha ? *alpha : variance), gr = out(want_r, r);
+  if (none || !(want_x || want_xu || want_lengthscale || want_variance || want_alpha || want_r))
+    return {gx, gxu, gl, gv, ga, gr};
+  const size_t ws_bytes = pa_gp_sgpr_workspace(a.dt, a.N, a.M, a.D, Q, 1, want_x, want_xu, (int)forced_splits);
+  at::Tensor ws = at::empty({(int64_t)((ws_bytes < 8 ? 8 : ws_bytes) + 7) / 8}, x.options().dtype(at::kDouble));
+  auto ptr = [](bool want, at::Tensor& t) -> void* { return want ? t.data_ptr() : nullptr; };
+  check(pa_gp_sgpr_bwd(a.dt, (int)family, x.data_ptr(), a.z, r.data_ptr(), lengthscale.data_ptr(), (int)lengthscale.numel(),
+                       variance.data_ptr(), a.alpha, gA.data_ptr(), gb.data_ptr(), a.N, a.M, a.D, Q, ptr(want_x, gx),
+                       ptr(want_xu, gxu), ptr(want_lengthscale, gl), ptr(want_variance, gv), ptr(want_alpha, ga),
+                       ptr(want_r, gr), (int)forced_splits, ws.data_ptr(), (size_t)ws.numel() * 8, current_stream()),
+        "gp_sgpr_bwd");
+  return {gx, gxu, gl, gv, ga, gr};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -937,6 +996,12 @@ TORCH_LIBRARY(pyro_amd, m) {
   m.def("gp_kernel_bwd(Tensor x, Tensor? z, Tensor lengthscale, Tensor variance, Tensor? alpha, Tensor G, int family, "
         "bool want_x, bool want_z, bool want_lengthscale, bool want_variance, bool want_alpha, int forced_splits) -> "
         "(Tensor gx, Tensor gz, Tensor g_lengthscale, Tensor g_variance, Tensor g_alpha)");
+  m.def("gp_sgpr(Tensor x, Tensor xu, Tensor r, Tensor lengthscale, Tensor variance, Tensor? alpha, int family, "
+        "int forced_splits) -> (Tensor A, Tensor b)");
+  m.def("gp_sgpr_bwd(Tensor x, Tensor xu, Tensor r, Tensor lengthscale, Tensor variance, Tensor? alpha, Tensor gA, "
+        "Tensor gb, int family, bool want_x, bool want_xu, bool want_lengthscale, bool want_variance, bool want_alpha, "
+        "bool want_r, int forced_splits) -> "
+        "(Tensor gx, Tensor gxu, Tensor g_lengthscale, Tensor g_variance, Tensor g_alpha, Tensor gr)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -975,6 +1040,8 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("time_transform", &time_transform);
   m.impl("gp_kernel", &gp_kernel);
   m.impl("gp_kernel_bwd", &gp_kernel_bwd);
+  m.impl("gp_sgpr", &gp_sgpr);
+  m.impl("gp_sgpr_bwd", &gp_sgpr_bwd);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

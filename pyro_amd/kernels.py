@@ -1202,6 +1202,77 @@ def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(Tru
     return gx, gz, g_ls, g_var, g_alpha
 
 
+GP_SGPR_MAX_M = {torch.float32: 512, torch.float64: 256}      # (csrc/gp_sgpr_plan.h gps_max_m)
+GP_SGPR_MAX_Q = 16
+
+
+def _gp_sgpr_args(x, xu, r, lengthscale, variance, alpha, family):
+    family, x, xu, lengthscale, variance, alpha = _gp_kernel_args(x, xu, lengthscale, variance, alpha, family)
+    _require_gpu(r)
+    assert xu is not None, "gp_sgpr: xu [M, D]"
+    N, M = x.shape[0], xu.shape[0]
+    assert r.dim() == 2 and r.shape[0] == N and r.dtype == x.dtype, "gp_sgpr: r [N, Q] of x's dtype"
+    Q = r.shape[1]
+    if M > GP_SGPR_MAX_M[x.dtype] or not 1 <= Q <= GP_SGPR_MAX_Q:
+        raise Unsupported("pyro_amd: gp_sgpr: M=%d over %d or Q=%d outside [1, %d]"
+                          % (M, GP_SGPR_MAX_M[x.dtype], Q, GP_SGPR_MAX_Q))
+    return family, x, xu, r.contiguous(), lengthscale, variance, alpha
+
+
+def _gp_sgpr_workspace(lib, x, N, M, D, Q, backward, want_gx, want_gxu, forced_splits):
+    nbytes = lib.pa_gp_sgpr_workspace(_dtype(x), N, M, D, Q, int(backward), int(want_gx), int(want_gxu), int(forced_splits))
+    return torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+
+
+def gp_sgpr_fwd(x, xu, r, lengthscale, variance, alpha=None, family="rbf", forced_splits=0):
+    """The statistics of a sparse GP regression without Kuf [M, N] in memory (pa_gp_sgpr_fwd): with
+    Kuf[i, n] = k(xu_i, x_n) of gp_kernel_fwd's families, (A [M, M] = Kuf Kuf^T, b [M, Q] = Kuf r).  x [N, D],
+    xu [M, D], r [N, Q]; parameters as for gp_kernel_fwd.  A is exactly symmetric; results are bit-reproducible.  M over
+    GP_SGPR_MAX_M[dtype] or Q outside [1, 16] raises Unsupported; N = 0 or M = 0 gives zeros without a launch."""
+    family, x, xu, r, lengthscale, variance, alpha = _gp_sgpr_args(x, xu, r, lengthscale, variance, alpha, family)
+    (N, D), M, Q = x.shape, xu.shape[0], r.shape[1]
+    if N == 0 or M == 0:
+        return x.new_zeros((M, M)), x.new_zeros((M, Q))
+    A, b = x.new_empty((M, M)), x.new_empty((M, Q))
+    lib = _lib.load()
+    ws = _gp_sgpr_workspace(lib, x, N, M, D, Q, False, False, False, forced_splits)
+    check(lib.pa_gp_sgpr_fwd(_dtype(x), family, _ptr(x), _ptr(xu), _ptr(r), _ptr(lengthscale), lengthscale.numel(),
+                             _ptr(variance), _ptr(alpha), _ptr(A), _ptr(b), N, M, D, Q, int(forced_splits), _ptr(ws),
+                             ws.numel() * 8, _stream()))
+    return A, b
+
+
+def gp_sgpr_bwd(x, xu, r, lengthscale, variance, alpha, gA, gb, family="rbf", want=(True,) * 6, forced_splits=0):
+    """The gradients of gp_sgpr_fwd given gA [M, M] (not assumed symmetric) and gb [M, Q]:
+    (gx, gxu, g_lengthscale, g_variance, g_alpha, gr), ``None`` where ``want`` is false (g_alpha also outside the
+    RationalQuadratic family).  G = (gA + gA^T) Kuf + gb r^T is formed block by block in registers, never in memory
+    (pa_gp_sgpr_bwd); fixed-order float64 sums: bit-reproducible."""
+    family, x, xu, r, lengthscale, variance, alpha = _gp_sgpr_args(x, xu, r, lengthscale, variance, alpha, family)
+    _require_gpu(gA, gb)
+    (N, D), M, Q = x.shape, xu.shape[0], r.shape[1]
+    assert tuple(gA.shape) == (M, M) and tuple(gb.shape) == (M, Q) and gA.dtype == gb.dtype == x.dtype, \
+        "gp_sgpr_bwd: gA [M, M], gb [M, Q] of x's dtype"
+    gA, gb = gA.contiguous(), gb.contiguous()
+    want_gx, want_gxu, want_ls, want_var, want_alpha, want_gr = (bool(w) for w in want)
+    want_alpha = want_alpha and alpha is not None
+    empty = N == 0 or M == 0
+    make = torch.zeros_like if empty else torch.empty_like
+    gx = make(x) if want_gx else None
+    gxu = make(xu) if want_gxu else None
+    g_ls = make(lengthscale) if want_ls else None
+    g_var = make(variance) if want_var else None
+    g_alpha = make(alpha) if want_alpha else None
+    gr = make(r) if want_gr else None
+    if empty or not (want_gx or want_gxu or want_ls or want_var or want_alpha or want_gr):
+        return gx, gxu, g_ls, g_var, g_alpha, gr
+    lib = _lib.load()
+    ws = _gp_sgpr_workspace(lib, x, N, M, D, Q, True, want_gx, want_gxu, forced_splits)
+    check(lib.pa_gp_sgpr_bwd(_dtype(x), family, _ptr(x), _ptr(xu), _ptr(r), _ptr(lengthscale), lengthscale.numel(),
+                             _ptr(variance), _ptr(alpha), _ptr(gA), _ptr(gb), N, M, D, Q, _ptr(gx), _ptr(gxu), _ptr(g_ls),
+                             _ptr(g_var), _ptr(g_alpha), _ptr(gr), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    return gx, gxu, g_ls, g_var, g_alpha, gr
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.
