@@ -1173,6 +1173,32 @@ int pa_gp_sgpr_bwd(int dtype, int family, const void* x, const void* xu, const v
                    int64_t Q, void* gx, void* gxu, void* g_lengthscale, void* g_variance, void* g_alpha, void* gr,
                    int forced_splits, void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_cond.hip: the per-point marginals of a sparse variational GP's conditional, streamed over the points ----
+ * With k_n = Kuf[:, n], Kuf[i, n] = k(xu_i, x_n) of the families above (same r2), J = 1 + Q:
+ *   pa_gp_cond_fwd:  loc [N, Q] = Kuf^T a,  s [N, J] with s[n, j] = |P_j k_n|^2.  a [M, Q]; Pt [J, M, M] holds the
+ *                    TRANSPOSES Pt_j = P_j^T; P_0 must be lower triangular (its upper triangle is not read).  One
+ *                    launch, one workgroup per 32 points, nothing of size M x N in memory, no workspace.
+ *   pa_gp_cond_bwd:  given g_loc [N, Q], g_s [N, J] and B2 [J, M, M] with B2_j = 2 P_j^T P_j (symmetric):
+ *                    ga [M, Q] = Kuf g_loc and Aw [J, M, M] in FLOAT64 for both dtypes, Aw_j = Kuf diag(g_s[:, j]) Kuf^T
+ *                    (exactly symmetric; the gradient of P_j is 2 P_j Aw_j) -- both or neither -- and, with G = a g_loc^T + sum_j B2_j Kuf
+ *                    diag(g_s[:, j]) formed block by block in registers, gx [N, D], gxu [M, D], g_lengthscale [n_ls],
+ *                    g_variance [1], g_alpha [1] as pa_gp_kernel_bwd would give for G.  NULL: not computed.
+ * All DEVICE pointers of one dtype, contiguous.  f32 runs the products on v_mfma_f32_32x32x2_f32, f64 on the VALU.
+ * 1 <= D <= 64, 1 <= Q <= 16, M <= 512 (f32) / 256 (f64), else PA_ERR_UNSUPPORTED.  The backward's partial records in
+ * ``workspace`` (pa_gp_cond_workspace bytes for the same shape and flags), summed in a fixed order in float64: no
+ * atomics, bit-reproducible.  forced_splits > 0 fixes the number of splits of N (tests).  N = 0 or M = 0: PA_OK
+ * without a launch. */
+size_t pa_gp_cond_workspace(int dtype, int64_t N, int64_t M, int64_t D, int64_t Q, int want_gx, int want_gxu,
+                            int forced_splits);
+int pa_gp_cond_fwd(int dtype, int family, const void* x, const void* xu, const void* a, const void* Pt,
+                   const void* lengthscale, int n_ls, const void* variance, const void* alpha, void* loc, void* s,
+                   int64_t N, int64_t M, int64_t D, int64_t Q, pa_stream_t stream);
+int pa_gp_cond_bwd(int dtype, int family, const void* x, const void* xu, const void* a, const void* B2,
+                   const void* lengthscale, int n_ls, const void* variance, const void* alpha, const void* g_loc,
+                   const void* g_s, int64_t N, int64_t M, int64_t D, int64_t Q, void* gx, void* gxu, void* g_lengthscale,
+                   void* g_variance, void* g_alpha, void* ga, void* Aw, int forced_splits, void* workspace,
+                   size_t workspace_bytes, pa_stream_t stream);
+
 /* Per-chain dense matrix x vector: y[c] = M[c] x[c] (transpose = 0) or M[c]^T x[c]
  * (transpose = 1); M[C, D, D] row-major with chain stride m_stride_chain elements (0 = one matrix
  * shared by all chains), x, y [C, D] contiguous, x != y.  Replaces the dense-block products of

@@ -379,6 +379,12 @@ _SIGNATURES = {
     "pa_gp_sgpr_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]                           # gA gb N M D Q
                        + [c_void_p] * 6 + [c_int, c_void_p, c_size_t, c_void_p]),                                # grads, splits ws stream
+    "pa_gp_cond_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int]),
+    "pa_gp_cond_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,  # .. x xu a Pt ls n_ls var
+                               c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),     # alpha loc s N M D Q stream
+    "pa_gp_cond_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,  # .. x xu a B2 ls n_ls var
+                               c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]                 # alpha g_loc g_s N M D Q
+                       + [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_void_p]),                                # grads, splits ws stream
     "pa_chain_matvec": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                 c_void_p]),
     "pa_bow_workspace": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -1,5 +1,6 @@
-"""Gaussian-process regression models (the classes and arguments of pyro/contrib/gp/models; the code is this
-package's): ``GPModel``, exact ``GPRegression`` and ``SparseGPRegression`` with the DTC, FITC and VFE approximations.
+"""Gaussian-process models (the classes and arguments of pyro/contrib/gp/models; the code is this package's):
+``GPModel``, exact ``GPRegression``, ``SparseGPRegression`` with the DTC, FITC and VFE approximations, and
+``VariationalSparseGP`` with a likelihood of ``likelihoods``.
 
 A model closes over its data: ``model()`` and ``guide()`` take no arguments, so an SVI step over them is eager (see
 ``util.train``).  Covariance matrices come from ``self.kernel``; on the device the stationary families form them in one
@@ -10,6 +11,12 @@ reference does; the fused kernel's backward recomputes what it needs from the in
 A = Kuf Kuf^T [M, M], b = Kuf r [M, Q], sum r^2 and sum_n k(x_n, x_n), and csrc/gp_sgpr.hip forms A and b (and their
 gradient) in one pass over X each way without Kuf [M, N] in memory; the rest is M x M algebra in torch
 (``streamed_log_prob``).
+
+``VariationalSparseGP`` needs the data only through the per-point marginals of f(X) given q(u), and has a STREAMED route
+for them too (``FUSED_VSGP``): csrc/gp_cond.hip forms loc[q, n] = k_n . a_q and s[n, j] = |P_j k_n|^2 (k_n = Kuf[:, n])
+one tile of 32 points at a time, with a [M, Q] and P [1 + Q, M, M] from M x M triangular solves in torch
+(``conditional_factors``); nothing of size M x N exists in either direction.  ``forward(Xnew)`` takes the same route.
+Float64 models only: float32 models run ``util.conditional`` (README "Gaussian processes" has the figures).
 """
 import math
 
@@ -18,14 +25,17 @@ from torch.distributions import constraints
 from torch.nn import Parameter
 
 from ... import distributions as dist
-from ... import primitives
+from ... import poutine, primitives
 from ...nn.module import PyroParam, pyro_method
 from .kernels import Isotropy
 from .parameterized import Parameterized
+from . import util
 from .util import conditional
 
 FUSED_SGPR = True                 # SparseGPRegression, DTC / VFE: the statistics from pa_gp_sgpr_fwd / pa_gp_sgpr_bwd
 FUSED_SGPR_MIN_N = 1000000        # ... from this many data points on (README "Gaussian processes": the sweep)
+FUSED_VSGP = True                 # VariationalSparseGP: the marginals from pa_gp_cond_fwd / pa_gp_cond_bwd
+FUSED_VSGP_MIN_N = float("inf")   # ... from this many points on (README "Gaussian processes": no swept N qualifies)
 
 
 def _zero_mean_function(x):
@@ -63,6 +73,47 @@ class _StreamedStatistics(torch.autograd.Function):
         return (gx, gxu, gr, None if gl is None else gl.reshape(lengthscale.shape),
                 None if gv is None else gv.reshape(variance.shape),
                 None if ga is None else ga.reshape(alpha.shape), None)
+
+
+class _ConditionalMarginals(torch.autograd.Function):
+    """(loc [N, Q], s [N, 1 + Q]) = (Kuf^T a, |P_j Kuf[:, n]|^2) in one pass over x; the gradient is two more passes
+    (weighted Grams for a and P, then the chain to x, xu and the kernel's parameters).  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, xu, a, P, lengthscale, variance, alpha, family):
+        from ... import kernels
+        ctx.family = family
+        ctx.save_for_backward(x, xu, a, P, lengthscale, variance, alpha)
+        return kernels.gp_cond_fwd(x, xu, a, P, lengthscale.reshape(-1), variance.reshape(-1),
+                                   None if alpha is None else alpha.reshape(-1), family)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loc, g_s):
+        from ... import kernels
+        x, xu, a, P, lengthscale, variance, alpha = ctx.saved_tensors
+        nx, nxu, na, nP, nl, nv, nal = ctx.needs_input_grad[:7]
+        gx, gxu, gl, gv, gal, ga, gP = kernels.gp_cond_bwd(
+            x, xu, a, P, lengthscale.reshape(-1), variance.reshape(-1), None if alpha is None else alpha.reshape(-1),
+            g_loc, g_s, ctx.family, (nx, nxu, nl, nv, nal, na, nP))
+        return (gx, gxu, ga, gP, None if gl is None else gl.reshape(lengthscale.shape),
+                None if gv is None else gv.reshape(variance.shape),
+                None if gal is None else gal.reshape(alpha.shape), None)
+
+
+def conditional_factors(Luu, u_loc, u_scale_tril, whiten):
+    """From q(u) = N(u_loc [Q, M], u_scale_tril [Q, M, M]) and the factor Luu of Kuu to what the streamed marginals
+    need: a [M, Q] and P [1 + Q, M, M] with loc[q, n] = k_n . a_q, var[q, n] = clamp(kd_n - |P_0 k_n|^2, 0) +
+    |P_{1+q} k_n|^2.  P_0 = Luu^-1; with ``whiten`` a = Luu^-T u_loc^T and P_{1+q} = S_q^T Luu^-1, else a = Kuu^-1 u_loc^T
+    and P_{1+q} = (Luu^-1 S_q)^T Luu^-1."""
+    M = Luu.size(0)
+    Linv = torch.linalg.solve_triangular(Luu, torch.eye(M, dtype=Luu.dtype, device=Luu.device), upper=False)
+    U = u_loc.t()
+    if not whiten:
+        U = torch.linalg.solve_triangular(Luu, U, upper=False)
+        u_scale_tril = torch.linalg.solve_triangular(Luu, u_scale_tril, upper=False)
+    a = torch.linalg.solve_triangular(Luu.t(), U, upper=True)
+    return a, torch.cat((Linv.unsqueeze(0), u_scale_tril.transpose(-1, -2).matmul(Linv)))
 
 
 def streamed_factors(Luu, A, b, noise):
@@ -330,4 +381,95 @@ class SparseGPRegression(GPModel):
             if not noiseless:
                 Kss_diag = Kss_diag + self.noise
             cov = (Kss_diag - Ws.pow(2).sum(dim=0) + Linv_Ws.pow(2).sum(dim=0)).expand(batch + (C,))
+        return loc + self.mean_function(Xnew), cov
+
+
+class VariationalSparseGP(GPModel):
+    """A sparse GP with a variational posterior q(u) = N(u_loc, u_scale_tril u_scale_tril^T) over the values at M
+    inducing inputs ``Xu`` [M, ...] (a parameter) and any ``likelihood``; trainable on mini-batches (``set_data`` with
+    ``num_data`` the size of the whole data set).  ``latent_shape`` is the batch shape of the latent functions (y's by
+    default); with ``whiten`` q describes v = Luu^-1 u instead."""
+
+    def __init__(self, X, y, kernel, Xu, likelihood, mean_function=None, latent_shape=None, num_data=None, whiten=False,
+                 jitter=1e-6):
+        assert isinstance(Xu, torch.Tensor), "Xu needs to be a torch Tensor instead of a {}".format(type(Xu))
+        super().__init__(X, y, kernel, mean_function, jitter)
+        self.likelihood = likelihood
+        self.Xu = Parameter(Xu)
+        y_batch_shape = self.y.shape[:-1] if self.y is not None else torch.Size([])
+        self.latent_shape = torch.Size(latent_shape) if latent_shape is not None else y_batch_shape
+        M = self.Xu.size(0)
+        self.u_loc = Parameter(self.Xu.new_zeros(self.latent_shape + (M,)))
+        identity = torch.eye(M, dtype=self.Xu.dtype, device=self.Xu.device)
+        self.u_scale_tril = PyroParam(identity.repeat(self.latent_shape + (1, 1)), constraints.lower_cholesky)
+        self.num_data = num_data if num_data is not None else self.X.size(0)
+        self.whiten = whiten
+
+    def _factor(self):
+        Kuu = self.kernel(self.Xu).contiguous()
+        return torch.linalg.cholesky(_add_to_diagonal(Kuu, self.jitter))
+
+    def _streamed(self, X, Luu):
+        """(loc, var) of f(X), each ``latent_shape + (N,)``, by the streamed route when it applies (module docstring), else
+        None.  Float64 models only: a float32 model cast up to the float64 kernels (Luu still factored in float32) missed
+        four times the dense float32 route's own error in three of the device test's eight cases (by 1.3, 1.6 and 5.0
+        times), so float32 models stay on the dense route."""
+        if not FUSED_VSGP or not isinstance(self.kernel, Isotropy):
+            return None
+        N, M, Q = X.size(0), self.Xu.size(0), self.latent_shape.numel()
+        if N < max(FUSED_VSGP_MIN_N, 1) or M < 1 or X.dtype != torch.float64:
+            return None
+        fused = self.kernel._fused(self.Xu, X)
+        from ... import kernels as hip
+        if fused is None or M > hip.GP_COND_MAX_M[torch.float64] or not 1 <= Q <= hip.GP_COND_MAX_Q:
+            return None
+        if not (self.u_loc.is_cuda and self.u_loc.dtype == X.dtype):
+            return None
+        xu, x, lengthscale, variance, alpha = fused
+        a, P = conditional_factors(Luu, self.u_loc.reshape(Q, M), self.u_scale_tril.reshape(Q, M, M), self.whiten)
+        loc, s = _ConditionalMarginals.apply(x, xu, a, P, lengthscale, variance, alpha, self.kernel._family)
+        var = (self.kernel(X, diag=True) - s[:, 0]).clamp(min=0) + s[:, 1:].t()
+        shape = self.latent_shape + (N,)
+        return loc.t().reshape(shape), var.reshape(shape)
+
+    def _marginals(self, X, Luu):
+        streamed = self._streamed(X, Luu)
+        if streamed is not None:
+            return streamed
+        return util.conditional(X, self.Xu, self.kernel, self.u_loc, self.u_scale_tril, Luu, full_cov=False,
+                                whiten=self.whiten, jitter=self.jitter)
+
+    @pyro_method
+    def model(self):
+        self.set_mode("model")
+        Luu = self._factor()
+        zero_loc = self.Xu.new_zeros(self.u_loc.shape)
+        prior_tril = torch.eye(Luu.size(0), dtype=Luu.dtype, device=Luu.device) if self.whiten else Luu
+        primitives.sample(self._pyro_get_fullname("u"),
+                          dist.MultivariateNormal(zero_loc, scale_tril=prior_tril).to_event(zero_loc.dim() - 1))
+        f_loc, f_var = self._marginals(self.X, Luu)
+        f_loc = f_loc + self.mean_function(self.X)
+        if self.y is None:
+            return f_loc, f_var
+        self.likelihood._load_pyro_samples()      # (the likelihood's own priors are not scaled)
+        with poutine.scale(scale=self.num_data / self.X.size(0)):
+            return self.likelihood(f_loc, f_var, self.y)
+
+    @pyro_method
+    def guide(self):
+        self.set_mode("guide")
+        self._load_pyro_samples()
+        primitives.sample(self._pyro_get_fullname("u"),
+                          dist.MultivariateNormal(self.u_loc, scale_tril=self.u_scale_tril).to_event(self.u_loc.dim() - 1))
+
+    def forward(self, Xnew, full_cov=False):
+        """Mean and covariance (``full_cov``) or variance of the posterior of f(Xnew); parameters are read from the
+        guide."""
+        self._check_Xnew_shape(Xnew)
+        self.set_mode("guide")
+        if full_cov:
+            loc, cov = util.conditional(Xnew, self.Xu, self.kernel, self.u_loc, self.u_scale_tril, full_cov=True,
+                                        whiten=self.whiten, jitter=self.jitter)
+        else:
+            loc, cov = self._marginals(Xnew, self._factor())
         return loc + self.mean_function(Xnew), cov

@@ -24,6 +24,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # (tools/probes/issue_probe.hip), so that file is built without SLP vectorisation.
 # glm_family.hip is the same frame with f32 MFMAs: same flag.
 FILE_FLAGS = {"glm.hip": ["-fno-slp-vectorize"], "glm_family.hip": ["-fno-slp-vectorize"]}
+# gp_cond.hip is compiled without the packed f32 instructions (v_pk_add / mul / fma_f32) altogether: nothing in it gains
+# from them, and its f32 results are then the scalar instructions' on every path
+FILE_FLAGS["gp_cond.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 if os.environ.get("PA_CHAIN_LATENCY_PROBE"):          # developer probe (tools/chain_stamps.py)
     FILE_FLAGS["chain.hip"] = ["-DPA_CHAIN_LATENCY_PROBE"]
 

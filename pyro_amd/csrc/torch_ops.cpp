@@ -801,6 +801,73 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   return {gx, gxu, gl, gv, ga, gr};
 }
 
+// the per-point marginals of a sparse variational GP's conditional streamed over the points (csrc/gp_cond.hip):
+// loc [N, Q] = Kuf^T a and s [N, 1 + Q], s[n, j] = |P_j Kuf[:, n]|^2, Kuf itself never in memory
+static int64_t gp_cond_check(const char* who, const GpArgs& g, const at::Tensor& x, const at::Tensor& a, const at::Tensor& P) {
+  auto same = [&](const at::Tensor& t) { return t.is_cuda() && t.scalar_type() == x.scalar_type(); };
+  TORCH_CHECK(g.z != nullptr && same(a) && same(P) && a.is_contiguous() && a.dim() == 2 && a.size(0) == g.M &&
+                  a.size(1) >= 1 && a.size(1) <= 16 && P.dim() == 3 && P.size(0) == a.size(1) + 1 && P.size(1) == g.M &&
+                  P.size(2) == g.M && g.M <= (g.dt == PA_F32 ? 512 : 256),
+              "pyro_amd::", who, ": xu [M, D], a [M, Q] contiguous, P [1 + Q, M, M] of x's dtype, 1 <= Q <= 16, "
+              "M <= 512 (f32) / 256 (f64)");
+  return a.size(1);
+}
+
+std::tuple<at::Tensor, at::Tensor> gp_cond(const at::Tensor& x, const at::Tensor& xu, const at::Tensor& a,
+                                           const at::Tensor& P, const at::Tensor& lengthscale, const at::Tensor& variance,
+                                           const std::optional<at::Tensor>& alpha, int64_t family) {
+  const GpArgs g = gp_args("gp_cond", x, xu, lengthscale, variance, alpha, family);
+  const int64_t Q = gp_cond_check("gp_cond", g, x, a, P);
+  if (g.N == 0 || g.M == 0) return {at::zeros({g.N, Q}, x.options()), at::zeros({g.N, Q + 1}, x.options())};
+  at::Tensor loc = at::empty({g.N, Q}, x.options()), s = at::empty({g.N, Q + 1}, x.options());
+  at::Tensor Pt = P.transpose(1, 2).contiguous();
+  check(pa_gp_cond_fwd(g.dt, (int)family, x.data_ptr(), g.z, a.data_ptr(), Pt.data_ptr(), lengthscale.data_ptr(),
+                       (int)lengthscale.numel(), variance.data_ptr(), g.alpha, loc.data_ptr(), s.data_ptr(), g.N, g.M, g.D,
+                       Q, current_stream()),
+        "gp_cond");
+  return {loc, s};
+}
+
+// its gradients given g_loc [N, Q] and g_s [N, 1 + Q]: (gx, gxu, g_lengthscale, g_variance, g_alpha, ga, gP), an empty
+// tensor where want_* is false (g_alpha also outside family 1); 2 P_j^T P_j and gP = 2 P Aw are formed here
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gp_cond_bwd(
+    const at::Tensor& x, const at::Tensor& xu, const at::Tensor& a, const at::Tensor& P, const at::Tensor& lengthscale,
+    const at::Tensor& variance, const std::optional<at::Tensor>& alpha, const at::Tensor& g_loc, const at::Tensor& g_s,
+    int64_t family, bool want_x, bool want_xu, bool want_lengthscale, bool want_variance, bool want_alpha, bool want_a,
+    bool want_P, int64_t forced_splits) {
+  const GpArgs g = gp_args("gp_cond_bwd", x, xu, lengthscale, variance, alpha, family);
+  const int64_t Q = gp_cond_check("gp_cond_bwd", g, x, a, P);
+  auto same = [&](const at::Tensor& t) { return t.is_cuda() && t.is_contiguous() && t.scalar_type() == x.scalar_type(); };
+  TORCH_CHECK(same(g_loc) && same(g_s) && g_loc.dim() == 2 && g_loc.size(0) == g.N && g_loc.size(1) == Q &&
+                  g_s.dim() == 2 && g_s.size(0) == g.N && g_s.size(1) == Q + 1 && forced_splits >= 0,
+              "pyro_amd::gp_cond_bwd: g_loc [N, Q], g_s [N, 1 + Q] contiguous, of x's dtype");
+  want_alpha = want_alpha && g.alpha != nullptr;
+  const bool none = g.N == 0 || g.M == 0, gram = want_a || want_P;
+  const bool chain = want_x || want_xu || want_lengthscale || want_variance || want_alpha;
+  auto out = [&](bool want, const at::Tensor& like) {
+    return want ? (none ? at::zeros_like(like) : at::empty_like(like)) : at::empty({0}, x.options());
+  };
+  at::Tensor gx = out(want_x, x), gxu = out(want_xu, xu), gl = out(want_lengthscale, lengthscale),
+             gv = out(want_variance, variance), gal = out(want_alpha, want_alpha ? *alpha : variance), ga = out(gram, a),
+             Aw = gram ? (none ? at::zeros(P.sizes(), x.options().dtype(at::kDouble))
+                               : at::empty(P.sizes(), x.options().dtype(at::kDouble)))
+                       : at::empty({0}, x.options());
+  if (!none && (gram || chain)) {
+    at::Tensor B2 = chain ? at::matmul(P.transpose(1, 2), P).mul_(2).contiguous() : P;
+    const size_t ws_bytes = pa_gp_cond_workspace(g.dt, g.N, g.M, g.D, Q, want_x, want_xu, (int)forced_splits);
+    at::Tensor ws = at::empty({(int64_t)((ws_bytes < 8 ? 8 : ws_bytes) + 7) / 8}, x.options().dtype(at::kDouble));
+    auto ptr = [](bool want, at::Tensor& t) -> void* { return want ? t.data_ptr() : nullptr; };
+    check(pa_gp_cond_bwd(g.dt, (int)family, x.data_ptr(), g.z, a.data_ptr(), B2.data_ptr(), lengthscale.data_ptr(),
+                         (int)lengthscale.numel(), variance.data_ptr(), g.alpha, g_loc.data_ptr(), g_s.data_ptr(), g.N, g.M,
+                         g.D, Q, ptr(want_x, gx), ptr(want_xu, gxu), ptr(want_lengthscale, gl), ptr(want_variance, gv),
+                         ptr(want_alpha, gal), ptr(gram, ga), ptr(gram, Aw), (int)forced_splits, ws.data_ptr(),
+                         (size_t)ws.numel() * 8, current_stream()),
+          "gp_cond_bwd");
+  }
+  at::Tensor gP = want_P ? at::matmul(P.to(at::kDouble), Aw).mul_(2).to(x.scalar_type()) : at::empty({0}, x.options());
+  return {gx, gxu, gl, gv, gal, want_a ? ga : at::empty({0}, x.options()), gP};
+}
+
 // the same chain decoded in one launch: its most probable path (mode 0) or one joint posterior draw (mode 1), with the
 // path's score / log Z (pyro/infer/discrete.py _sample_posterior_from_trace on a pyro.markov model).  pairwise
 // [B | 1, T - 1 | 1, K, K] as for logchain (anything for T = 1); seed / offset: the 64-bit words as two's complement
@@ -1002,6 +1069,12 @@ TORCH_LIBRARY(pyro_amd, m) {
         "Tensor gb, int family, bool want_x, bool want_xu, bool want_lengthscale, bool want_variance, bool want_alpha, "
         "bool want_r, int forced_splits) -> "
         "(Tensor gx, Tensor gxu, Tensor g_lengthscale, Tensor g_variance, Tensor g_alpha, Tensor gr)");
+  m.def("gp_cond(Tensor x, Tensor xu, Tensor a, Tensor P, Tensor lengthscale, Tensor variance, Tensor? alpha, "
+        "int family) -> (Tensor loc, Tensor s)");
+  m.def("gp_cond_bwd(Tensor x, Tensor xu, Tensor a, Tensor P, Tensor lengthscale, Tensor variance, Tensor? alpha, "
+        "Tensor g_loc, Tensor g_s, int family, bool want_x, bool want_xu, bool want_lengthscale, bool want_variance, "
+        "bool want_alpha, bool want_a, bool want_P, int forced_splits) -> "
+        "(Tensor gx, Tensor gxu, Tensor g_lengthscale, Tensor g_variance, Tensor g_alpha, Tensor ga, Tensor gP)");
   m.def("mixture_fwd_bwd(int dist, Tensor x, Tensor a, Tensor p0, Tensor? p1) -> Tensor");
   m.def("lda_factor_indexed(Tensor words, Tensor index, Tensor log_theta, Tensor log_phi) -> "
         "(Tensor out_doc, Tensor g_theta, Tensor g_phi)");
@@ -1042,6 +1115,8 @@ TORCH_LIBRARY_IMPL(pyro_amd, CUDA, m) {
   m.impl("gp_kernel_bwd", &gp_kernel_bwd);
   m.impl("gp_sgpr", &gp_sgpr);
   m.impl("gp_sgpr_bwd", &gp_sgpr_bwd);
+  m.impl("gp_cond", &gp_cond);
+  m.impl("gp_cond_bwd", &gp_cond_bwd);
   m.impl("mixture_fwd_bwd", &mixture_fwd_bwd);
   m.impl("lda_factor_indexed", &lda_factor_indexed);
   m.impl("tall_linear_act", &tall_linear_act);

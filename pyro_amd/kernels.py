@@ -1273,6 +1273,81 @@ def gp_sgpr_bwd(x, xu, r, lengthscale, variance, alpha, gA, gb, family="rbf", wa
     return gx, gxu, g_ls, g_var, g_alpha, gr
 
 
+GP_COND_MAX_M = {torch.float32: 512, torch.float64: 256}      # (csrc/gp_cond_plan.h: gp_sgpr_plan.h's gps_max_m)
+GP_COND_MAX_Q = 16
+
+
+def _gp_cond_args(x, xu, a, P, lengthscale, variance, alpha, family):
+    family, x, xu, lengthscale, variance, alpha = _gp_kernel_args(x, xu, lengthscale, variance, alpha, family)
+    _require_gpu(a, P)
+    assert xu is not None, "gp_cond: xu [M, D]"
+    M = xu.shape[0]
+    assert a.dim() == 2 and a.shape[0] == M and a.dtype == x.dtype, "gp_cond: a [M, Q] of x's dtype"
+    Q = a.shape[1]
+    assert tuple(P.shape) == (Q + 1, M, M) and P.dtype == x.dtype, "gp_cond: P [1 + Q, M, M] of x's dtype"
+    if M > GP_COND_MAX_M[x.dtype] or not 1 <= Q <= GP_COND_MAX_Q:
+        raise Unsupported("pyro_amd: gp_cond: M=%d over %d or Q=%d outside [1, %d]"
+                          % (M, GP_COND_MAX_M[x.dtype], Q, GP_COND_MAX_Q))
+    return family, x, xu, a.contiguous(), P, lengthscale, variance, alpha
+
+
+def gp_cond_fwd(x, xu, a, P, lengthscale, variance, alpha=None, family="rbf"):
+    """The per-point marginals of a sparse GP's conditional without Kuf [M, N] in memory (pa_gp_cond_fwd): with
+    k_n = Kuf[:, n], Kuf[i, n] = k(xu_i, x_n) of gp_kernel_fwd's families, (loc [N, Q] = Kuf^T a, s [N, 1 + Q] with
+    s[n, j] = |P_j k_n|^2), ONE launch.  x [N, D], xu [M, D], a [M, Q], P [1 + Q, M, M] with P[0] lower triangular
+    (its upper triangle is not read); parameters as for gp_kernel_fwd.  M over GP_COND_MAX_M[dtype] or Q outside [1, 16]
+    raises Unsupported; N = 0 or M = 0 gives zeros without a launch."""
+    family, x, xu, a, P, lengthscale, variance, alpha = _gp_cond_args(x, xu, a, P, lengthscale, variance, alpha, family)
+    (N, D), M, Q = x.shape, xu.shape[0], a.shape[1]
+    if N == 0 or M == 0:
+        return x.new_zeros((N, Q)), x.new_zeros((N, Q + 1))
+    loc, s = x.new_empty((N, Q)), x.new_empty((N, Q + 1))
+    Pt = P.transpose(-1, -2).contiguous()      # (the kernel reads 32 rows of P_j at one inner index as consecutive words)
+    check(_lib.load().pa_gp_cond_fwd(_dtype(x), family, _ptr(x), _ptr(xu), _ptr(a), _ptr(Pt), _ptr(lengthscale),
+                                     lengthscale.numel(), _ptr(variance), _ptr(alpha), _ptr(loc), _ptr(s), N, M, D, Q,
+                                     _stream()))
+    return loc, s
+
+
+def gp_cond_bwd(x, xu, a, P, lengthscale, variance, alpha, g_loc, g_s, family="rbf", want=(True,) * 7, forced_splits=0):
+    """The gradients of gp_cond_fwd given g_loc [N, Q] and g_s [N, 1 + Q]:
+    (gx, gxu, g_lengthscale, g_variance, g_alpha, ga, gP), ``None`` where ``want`` is false (g_alpha also outside the
+    RationalQuadratic family).  Two passes over x (pa_gp_cond_bwd): the weighted Grams Aw_j = Kuf diag(g_s[:, j]) Kuf^T
+    with ga = Kuf g_loc, and the chain of G = a g_loc^T + 2 sum_j P_j^T P_j Kuf diag(g_s[:, j]), which is formed block by
+    block in registers.  B_j = P_j^T P_j and gP = 2 P Aw are M x M products in torch.  Fixed-order float64 sums:
+    bit-reproducible."""
+    family, x, xu, a, P, lengthscale, variance, alpha = _gp_cond_args(x, xu, a, P, lengthscale, variance, alpha, family)
+    _require_gpu(g_loc, g_s)
+    (N, D), M, Q = x.shape, xu.shape[0], a.shape[1]
+    assert tuple(g_loc.shape) == (N, Q) and tuple(g_s.shape) == (N, Q + 1) and g_loc.dtype == g_s.dtype == x.dtype, \
+        "gp_cond_bwd: g_loc [N, Q], g_s [N, 1 + Q] of x's dtype"
+    g_loc, g_s = g_loc.contiguous(), g_s.contiguous()
+    want_gx, want_gxu, want_ls, want_var, want_alpha, want_ga, want_gP = (bool(w) for w in want)
+    want_alpha = want_alpha and alpha is not None
+    gram = want_ga or want_gP
+    chain = want_gx or want_gxu or want_ls or want_var or want_alpha
+    empty = N == 0 or M == 0
+    make = torch.zeros_like if empty else torch.empty_like
+    gx = make(x) if want_gx else None
+    gxu = make(xu) if want_gxu else None
+    g_ls = make(lengthscale) if want_ls else None
+    g_var = make(variance) if want_var else None
+    g_alpha = make(alpha) if want_alpha else None
+    ga = make(a) if gram else None
+    Aw = (torch.zeros if empty else torch.empty)(P.shape, dtype=torch.float64, device=x.device) if gram else None
+    if not empty and (gram or chain):
+        lib = _lib.load()
+        B2 = (2 * P.transpose(-1, -2).matmul(P)).contiguous() if chain else P      # (symmetric; only the chain reads it)
+        nbytes = lib.pa_gp_cond_workspace(_dtype(x), N, M, D, Q, int(want_gx), int(want_gxu), int(forced_splits))
+        ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+        check(lib.pa_gp_cond_bwd(_dtype(x), family, _ptr(x), _ptr(xu), _ptr(a), _ptr(B2), _ptr(lengthscale),
+                                 lengthscale.numel(), _ptr(variance), _ptr(alpha), _ptr(g_loc), _ptr(g_s), N, M, D, Q,
+                                 _ptr(gx), _ptr(gxu), _ptr(g_ls), _ptr(g_var), _ptr(g_alpha), _ptr(ga), _ptr(Aw),
+                                 int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    gP = (2 * P.double().matmul(Aw)).to(x.dtype) if want_gP else None      # (Aw is float64 for both dtypes)
+    return gx, gxu, g_ls, g_var, g_alpha, ga if want_ga else None, gP
+
+
 def mvn_tril_sample(loc, rho, A, P, seed=0, offset=0, offset_dev=None, eps=None):
     """Full-covariance Normal guide draw for P particles (pa_mvn_tril_sample): loc, rho [n],
     A [n, n] unconstrained; ``eps`` [P, n] given = use it instead of the Philox stream.

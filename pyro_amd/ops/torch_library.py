@@ -209,6 +209,20 @@ def _register():
         return (out(want_x, x), out(want_xu, xu), out(want_lengthscale, lengthscale), out(want_variance, variance),
                 out(want_alpha, alpha if want_alpha else variance), out(want_r, r))
 
+    @lib.register_fake("pyro_amd::gp_cond")
+    def _(x, xu, a, P, lengthscale, variance, alpha, family):
+        return x.new_empty((x.shape[0], a.shape[1])), x.new_empty((x.shape[0], a.shape[1] + 1))
+
+    @lib.register_fake("pyro_amd::gp_cond_bwd")
+    def _(x, xu, a, P, lengthscale, variance, alpha, g_loc, g_s, family, want_x, want_xu, want_lengthscale,
+          want_variance, want_alpha, want_a, want_P, forced_splits):
+        def out(want, like):
+            return torch.empty_like(like) if want else x.new_empty((0,))
+        want_alpha = want_alpha and alpha is not None
+        return (out(want_x, x), out(want_xu, xu), out(want_lengthscale, lengthscale), out(want_variance, variance),
+                out(want_alpha, alpha if want_alpha else variance), out(want_a, a),
+                x.new_empty(P.shape) if want_P else x.new_empty((0,)))
+
     @lib.register_fake("pyro_amd::mixture_fwd_bwd")
     def _(dist, x, a, p0, p1):
         return x.new_empty((a.shape[0], 1 + 3 * a.shape[1]), dtype=torch.float64)
@@ -692,4 +706,4 @@ TYPED_OPS = ("dist_log_prob_sum", "multi_log_prob_sum", "meanfield_normal_sample
              "mvn_tril_sample", "logsumexp_terms", "logchain", "logchain_decode", "mixture_fwd_bwd", "lda_factor_indexed", "tall_linear_act",
              "nuts_tree_run_advance", "gaussian_hmm", "gaussian_hmm_sample", "gaussian_hmm_draw",
              "gaussian_hmm_smooth", "gamma_gaussian_hmm", "linear_hmm_draw", "forecast_scores", "time_transform",
-             "gp_kernel", "gp_kernel_bwd", "gp_sgpr", "gp_sgpr_bwd")
+             "gp_kernel", "gp_kernel_bwd", "gp_sgpr", "gp_sgpr_bwd", "gp_cond", "gp_cond_bwd")
