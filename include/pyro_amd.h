@@ -1152,6 +1152,26 @@ int pa_gp_kernel_bwd(int dtype, int family, const void* x, const void* z, const 
                      void* gz, void* g_lengthscale, void* g_variance, void* g_alpha, int forced_splits, void* workspace,
                      size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_periodic.hip: the periodic covariance matrix, by direct differences with an exact range reduction -----
+ * Replaces pyro/contrib/gp/kernels/periodic.py (a [N, M, D] tensor of differences and four more passes of that size):
+ *   K[i, j] = variance * exp(-2 sum_k sin^2(pi (x_ik - z_jk) / p_k) / l_k^2)
+ * x [N, D], z [M, D] contiguous (z = NULL: z = x, M = N), lengthscale [n_ls] and period [n_period], each of 1 or D
+ * elements independently, variance [1], all of one dtype (f32 / f64) and all DEVICE pointers.  1 <= D <= 64, else
+ * PA_ERR_UNSUPPORTED.  The contract is pa_gp_kernel_*'s: the forward is ONE launch that writes K once (N = 0 or M = 0:
+ * PA_OK without a launch); the backward recomputes K from the inputs, reads G [N, M] once per side that wants a
+ * gradient (two reads in one pass for z = NULL), computes only the outputs that are not NULL -- gx [N, D], gz [M, D]
+ * (needs z), g_lengthscale [n_ls], g_period [n_period], g_variance [1] -- and sums partial records in ``workspace``
+ * (pa_gp_periodic_bwd_workspace bytes for the same shape and flags) in a fixed order in float64: no atomics,
+ * bit-reproducible.  forced_splits > 0 fixes the number of column splits (tests). */
+int pa_gp_periodic_fwd(int dtype, const void* x, const void* z, const void* lengthscale, int n_ls, const void* period,
+                       int n_period, const void* variance, void* K, int64_t N, int64_t M, int64_t D, pa_stream_t stream);
+size_t pa_gp_periodic_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int want_gx, int want_gz,
+                                    int forced_splits);
+int pa_gp_periodic_bwd(int dtype, const void* x, const void* z, const void* lengthscale, int n_ls, const void* period,
+                       int n_period, const void* variance, const void* G, int64_t N, int64_t M, int64_t D, void* gx,
+                       void* gz, void* g_lengthscale, void* g_period, void* g_variance, int forced_splits,
+                       void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* ---- csrc/gp_sgpr.hip: the statistics of a sparse GP regression (DTC / VFE), streamed: Kuf [M, N] is never formed --
  * With Kuf[i, n] = k(xu_i, x_n) of the families above (same r2: direct differences, float64 up to the exponential):
  *   pa_gp_sgpr_fwd:  A [M, M] = Kuf Kuf^T (both triangles written, exactly symmetric),  b [M, Q] = Kuf r

@@ -372,6 +372,12 @@ _SIGNATURES = {
     "pa_gp_kernel_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                  c_void_p, c_int64, c_int64, c_int64]                                    # G N M D
                          + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),                      # grads, splits ws stream
+    "pa_gp_periodic_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,  # .. x z ls n_ls period n_p var
+                                   c_void_p, c_int64, c_int64, c_int64, c_void_p]),                        # K N M D stream
+    "pa_gp_periodic_bwd_workspace": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_periodic_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_int64, c_int64, c_int64]                                    # G N M D
+                           + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),                      # grads, splits ws stream
     "pa_gp_sgpr_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
     "pa_gp_sgpr_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,  # .. x xu r ls n_ls var alpha
                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,                           # A b N M D Q

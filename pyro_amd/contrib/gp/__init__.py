@@ -1,10 +1,10 @@
 """Gaussian processes (reference: pyro/contrib/gp): ``Parameterized``, the kernel classes, exact and sparse GP
 regression, ``VariationalSparseGP`` with the likelihoods, ``util.conditional`` and ``util.train``.  On the device the
 stationary kernels form their covariance matrix and its gradient with csrc/gp_kernel.hip
-(``kernels.FUSED_GP_KERNEL``); sparse regression and the sparse variational model stream their statistics over the data
-(csrc/gp_sgpr.hip, csrc/gp_cond.hip).
+(``kernels.FUSED_GP_KERNEL``) and ``Periodic`` with csrc/gp_periodic.hip (``kernels.FUSED_GP_PERIODIC``); sparse
+regression and the sparse variational model stream their statistics over the data (csrc/gp_sgpr.hip, csrc/gp_cond.hip).
 
-Not here: VariationalGP and GPLVM; the Periodic, Cosine, Brownian, Polynomial,
+Not here: VariationalGP and GPLVM; the Cosine, Brownian, Polynomial,
 Coregionalize, Exponent, VerticalScaling and Warping kernels."""
 from . import kernels, likelihoods, models, util
 from .parameterized import Parameterized

@@ -1,6 +1,6 @@
 """Covariance functions of Gaussian-process models (the classes and arguments of pyro/contrib/gp/kernels; the code
 is this package's): the stationary families ``RBF``, ``RationalQuadratic``, ``Exponential``, ``Matern32``,
-``Matern52`` over ``Isotropy``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``.
+``Matern52`` over ``Isotropy``; ``Periodic``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``.
 
 A stationary family has two routes, chosen in ``Isotropy.forward``.
 
@@ -17,6 +17,10 @@ The two routes differ ON PURPOSE in how r2 is formed: the expansion cancels (in 
 ``Exponential`` at nearby points and useless for inputs shifted by 1e3), differences do not.  They describe the same
 function and agree to the conditioning of the expansion.  ``diag=True`` never launches.
 
+``Periodic`` has the same two routes under ``FUSED_GP_PERIODIC`` (csrc/gp_periodic.hip; a lengthscale and a period of 1
+or D elements each).  Its torch route is the reference's formula with [N, M, D] temporaries, ``D`` times the size of
+anything the kernel route allocates; both form the difference first, so they agree to the rounding of the angle.
+
 GP training is eager: the modules close over their data, so an SVI step over them is not captured into a graph
 (``util.train``, or ``SVI(..., hip_graph=False)``), and ``torch.linalg.cholesky`` synchronises in any case.
 """
@@ -31,6 +35,7 @@ from ...ops.torch_library import dispatcher_op as _dispatcher_op
 from .parameterized import Parameterized
 
 FUSED_GP_KERNEL = True            # device f32 / f64, D <= kernels.GP_KERNEL_MAX_D: pa_gp_kernel_fwd / pa_gp_kernel_bwd
+FUSED_GP_PERIODIC = True          # the same conditions for Periodic: pa_gp_periodic_fwd / pa_gp_periodic_bwd
 
 
 @_dispatcher_op("gp_kernel")
@@ -234,6 +239,79 @@ class Matern52(Isotropy):
         r2 = self._square_scaled_dist(X, Z)
         sr = math.sqrt(5.0) * (r2 + 1e-12).sqrt()
         return self.variance * (1 + sr + (5.0 / 3.0) * r2) * torch.exp(-sr)
+
+
+# ---- the periodic kernel ---------------------------------------------------------------------------------------------
+@_dispatcher_op("gp_periodic")
+class _PeriodicCovariance(torch.autograd.Function):
+    """K = variance * exp(-2 sum_k sin^2(pi (x - z) / p_k) / l_k^2) in ONE launch; the gradient recomputes K from the
+    saved INPUTS (the output may be modified in place by the caller), one pass over the incoming gradient per side."""
+
+    @staticmethod
+    def forward(ctx, x, z, lengthscale, period, variance):
+        from ... import kernels
+        ctx.save_for_backward(x, z, lengthscale, period, variance)
+        return kernels.gp_periodic_fwd(x, z, lengthscale.reshape(-1), period.reshape(-1), variance.reshape(-1))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ... import kernels
+        x, z, lengthscale, period, variance = ctx.saved_tensors
+        grads = kernels.gp_periodic_bwd(x, z, lengthscale.reshape(-1), period.reshape(-1), variance.reshape(-1), g,
+                                        list(ctx.needs_input_grad[:5]))
+        shapes = (None, None, lengthscale.shape, period.shape, variance.shape)
+        return tuple(t if t is None or s is None else t.reshape(s) for t, s in zip(grads, shapes))
+
+
+class Periodic(Kernel):
+    """variance * exp(-2 sum_k sin^2(pi (x_k - z_k) / period_k) / lengthscale_k^2).  ``lengthscale`` and ``period`` have
+    1 or ``input_dim`` elements, independently."""
+
+    def __init__(self, input_dim, variance=None, lengthscale=None, period=None, active_dims=None):
+        super().__init__(input_dim, active_dims)
+        variance = torch.tensor(1.0) if variance is None else variance
+        self.variance = PyroParam(variance, constraints.positive)
+        lengthscale = torch.tensor(1.0) if lengthscale is None else lengthscale
+        self.lengthscale = PyroParam(lengthscale, constraints.positive)
+        period = torch.tensor(1.0) if period is None else period
+        self.period = PyroParam(period, constraints.positive)
+
+    def _fused(self, X, Z):
+        """The contiguous sliced inputs and the parameters when the kernel route applies, else None."""
+        if not FUSED_GP_PERIODIC:
+            return None
+        variance, lengthscale, period = self.variance, self.lengthscale, self.period
+        tensors = [X, variance, lengthscale, period] + ([] if Z is None else [Z])
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == X.dtype for t in tensors):
+            return None
+        if X.dtype not in (torch.float32, torch.float64) or X.dim() > 2 or (Z is not None and Z.dim() > 2):
+            return None
+        Xs = self._slice_input(X).contiguous()
+        Zs = None if Z is None else self._slice_input(Z).contiguous()
+        D = Xs.size(1)
+        if Zs is not None and Zs.size(1) != D:
+            raise ValueError("Inputs must have the same number of features.")
+        from ... import kernels as hip
+        if not 1 <= D <= hip.GP_KERNEL_MAX_D or variance.numel() != 1:
+            return None
+        if any(p.numel() not in (1, D) or p.dim() > 1 for p in (lengthscale, period)):
+            return None
+        return Xs, Zs, lengthscale, period, variance
+
+    def forward(self, X, Z=None, diag=False):
+        if diag:
+            return self.variance.expand(X.size(0))
+        fused = self._fused(X, Z)
+        if fused is not None:
+            return _PeriodicCovariance.invoke(*fused)
+        # the torch route: the reference's formula, with its [N, M, D] temporaries
+        X = self._slice_input(X)
+        Z = X if Z is None else self._slice_input(Z)
+        if X.size(1) != Z.size(1):
+            raise ValueError("Inputs must have the same number of features.")
+        theta = (X[:, None, :] - Z[None, :, :]) * (math.pi / self.period)
+        return self.variance * torch.exp(-2 * (torch.sin(theta) / self.lengthscale).pow(2).sum(-1))
 
 
 # ---- kernels that do not depend on a distance ----------------------------------------------------------------------

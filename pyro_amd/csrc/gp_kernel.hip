@@ -35,15 +35,9 @@
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage): no instantiation uses scratch; LDS is
 // dynamic (gp_kernel_plan.h); forward 62 (f32) / 80 (f64) VGPRs, 8 / 6 waves per SIMD; backward 186-214 (f32, 2
 // waves) and 255-256 with up to 100 AGPRs (f64, 2 or 1 waves); the table is in the README entry "Gaussian processes".
-#include "common.h"
-#include "gp_kernel_plan.h"
+#include "gp_tile.h"
 
 namespace pa {
-
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
 
 // ---- the families: f(r2) and f'(r2) = df / d(r2), the guard inside --------------------------------------------------
 template <typename T>
@@ -60,18 +54,6 @@ template <typename T>
 __device__ __forceinline__ T gp_log1p(T v) {
   if constexpr (sizeof(T) == 4) return log1pf(v);
   else return log1p(v);
-}
-
-// exp(a) for an argument held in float64.  In float32 the argument is split into its rounded value and the remainder,
-// exp(hi + lo) = exp(hi) (1 + lo): rounding a = -r2 / 2 to float32 alone would cost |a| 2^-24 relative (4e-6 at r2 = 130).
-template <typename T>
-__device__ __forceinline__ T gp_exp_of(double a) {
-  if constexpr (sizeof(T) == 8) {
-    return exp(a);
-  } else {
-    const float hi = (float)a, lo = (float)(a - (double)hi);
-    return expf(hi) * (1.0f + lo);
-  }
 }
 
 // eval(r2 in float64, alpha) -> f, df = df / d(r2), da = df / d(alpha)
@@ -121,17 +103,6 @@ struct GpMatern52 {
     da = T(0);
   }
 };
-
-// ---- staging: rows [first, first + 64) of p [n, D] into tile [64, stride], zeros past the end ----------------------
-template <typename T>
-__device__ __forceinline__ void gp_stage(const T* __restrict__ p, int64_t first, int64_t n, int D, int stride, T* tile) {
-  const int total = GPK_TILE * D;
-  for (int e = threadIdx.x; e < total; e += GPK_THREADS) {
-    const int row = e / D, k = e - row * D;
-    const int64_t i = first + row;
-    tile[row * stride + k] = i < n ? p[i * D + k] : T(0);
-  }
-}
 
 template <typename T>
 __device__ __forceinline__ void gp_inverse_lengthscale(const T* __restrict__ ls, int n_ls, int D, double* inv_l) {
@@ -214,16 +185,6 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_fwd_kernel(const T* __r
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
-// sum over the 16 lanes of a DPP row (the lanes that share ty); every lane of the wave must be active
-template <typename T>
-__device__ __forceinline__ T gp_row16_sum(T v) {
-  v += dpp_get<0xB1>(v);
-  v += dpp_get<0x4E>(v);
-  v += dpp_get<0x141>(v);
-  v += dpp_get<0x140>(v);
-  return v;
-}
-
 template <typename T>
 struct GpBwdArgs {
   const T *xr, *xc;            // the points that get a gradient [R, D], the points that are walked [C, D]
@@ -236,34 +197,6 @@ struct GpBwdArgs {
   int64_t R, C, tiles_per_split, col_tiles;
   double *row_rec, *sc_rec;    // [splits, R, D], [workgroups, GPK_SCALARS + D]
 };
-
-template <typename T>
-__device__ __forceinline__ void gp_load_g(const GpBwdArgs<T>& a, int64_t sr, int64_t sc, int64_t i0, int64_t j0, int ty,
-                                          int tx, T (&g)[4][4]) {
-  // G(i, j) at i * sr + j * sc for the thread's 4 x 4 entries, zero outside [R, C]
-  const int64_t i = i0 + 4 * ty, j = j0 + 4 * tx;
-  const bool inside = i + 3 < a.R && j + 3 < a.C && (uintptr_t)a.G % sizeof(Vec4<T>) == 0;
-  if (sc == 1 && inside && (sr & 3) == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const Vec4<T> v = *reinterpret_cast<const Vec4<T>*>(a.G + (i + r) * sr + j);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) g[r][c] = v.v[c];
-    }
-  } else if (sr == 1 && inside && (sc & 3) == 0) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const Vec4<T> v = *reinterpret_cast<const Vec4<T>*>(a.G + (j + c) * sc + i);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) g[r][c] = v.v[r];
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) g[r][c] = (i + r < a.R && j + c < a.C) ? a.G[(i + r) * sr + (j + c) * sc] : T(0);
-  }
-}
 
 template <typename T, template <typename> class FAM>
 __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_bwd_kernel(const GpBwdArgs<T> a) {

@@ -1202,6 +1202,68 @@ def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(Tru
     return gx, gz, g_ls, g_var, g_alpha
 
 
+def _gp_periodic_args(x, z, lengthscale, period, variance):
+    _require_gpu(x, z, lengthscale, period, variance)
+    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_periodic: x [N, D], z [M, D]"
+    D = x.shape[1]
+    if not 1 <= D <= GP_KERNEL_MAX_D:
+        raise Unsupported("pyro_amd: gp_periodic: D=%d outside [1, %d]" % (D, GP_KERNEL_MAX_D))
+    for t in (z, lengthscale, period, variance):
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError("pyro_amd: gp_periodic: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    if lengthscale.numel() not in (1, D) or period.numel() not in (1, D) or variance.numel() != 1:
+        raise ValueError("pyro_amd: gp_periodic: lengthscale and period have 1 or D elements each, variance 1")
+    return (x.contiguous(), None if z is None else z.contiguous(), lengthscale.contiguous(), period.contiguous(),
+            variance.contiguous())
+
+
+def gp_periodic_fwd(x, z, lengthscale, period, variance):
+    """K [N, M] = variance * exp(-2 sum_k sin^2(pi (x_ik - z_jk) / p_k) / l_k^2) by direct differences with an exact
+    range reduction, ONE launch (pa_gp_periodic_fwd).  x [N, D], z [M, D] or None for z = x; lengthscale and period of 1 or
+    D elements each, variance of one: device tensors of x's dtype (f32 / f64), read by the kernel.  D over
+    GP_KERNEL_MAX_D raises Unsupported; an empty result makes no launch."""
+    x, z, lengthscale, period, variance = _gp_periodic_args(x, z, lengthscale, period, variance)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    K = x.new_empty((N, M))
+    if N == 0 or M == 0:
+        return K
+    check(_lib.load().pa_gp_periodic_fwd(_dtype(x), _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(period),
+                                         period.numel(), _ptr(variance), _ptr(K), N, M, D, _stream()))
+    return K
+
+
+def gp_periodic_bwd(x, z, lengthscale, period, variance, G, want=(True, True, True, True, True), forced_splits=0):
+    """The gradients of gp_periodic_fwd's K given G = dL/dK [N, M]: (gx, gz, g_lengthscale, g_period, g_variance), ``None``
+    where ``want`` is false (gz also when z is None: gx then takes both roles).  K is recomputed from the inputs -- it
+    is not an argument -- in one pass over G per side that wants a gradient, then a fixed-order float64 finalize
+    (pa_gp_periodic_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the number of column splits (tests)."""
+    x, z, lengthscale, period, variance = _gp_periodic_args(x, z, lengthscale, period, variance)
+    _require_gpu(G)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_periodic_bwd: G [N, M] of x's dtype"
+    G = G.contiguous()
+    want_gx, want_gz, want_ls, want_period, want_var = (bool(w) for w in want)
+    want_gz = want_gz and z is not None
+    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
+    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
+    gx = make(x) if want_gx else None
+    gz = make(z) if want_gz else None
+    g_ls = make(lengthscale) if want_ls else None
+    g_period = make(period) if want_period else None
+    g_var = make(variance) if want_var else None
+    if empty or not (want_gx or want_gz or want_ls or want_period or want_var):
+        return gx, gz, g_ls, g_period, g_var
+    lib = _lib.load()
+    nbytes = lib.pa_gp_periodic_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    check(lib.pa_gp_periodic_bwd(_dtype(x), _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(period),
+                                 period.numel(), _ptr(variance), _ptr(G), N, M, D, _ptr(gx), _ptr(gz), _ptr(g_ls),
+                                 _ptr(g_period), _ptr(g_var), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    return gx, gz, g_ls, g_period, g_var
+
+
 GP_SGPR_MAX_M = {torch.float32: 512, torch.float64: 256}      # (csrc/gp_sgpr_plan.h gps_max_m)
 GP_SGPR_MAX_Q = 16
 

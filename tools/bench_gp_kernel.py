@@ -4,11 +4,14 @@ routes of the same tree:
     torch    ``kernels.FUSED_GP_KERNEL = False``: the reference's expansion in torch operators (the baseline: the parent
              commit has no GP route at all)
 
-    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr]
+    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr|periodic|periodic_gpr]
 
 covariance   K(Xu, X) forward plus backward, Matern52 with ARD lengthscales, [512, 8] against [100000, 8], f32
 sgpr         one differentiable_loss + backward of SparseGPRegression, N = 1e5, M = 512, D = 8, f32, VFE
 gpr          one differentiable_loss + backward of GPRegression, N = 4096, D = 8, f32 and f64
+periodic     K(Xu, X) forward plus backward of Periodic with ARD lengthscales and periods (csrc/gp_periodic.hip against
+             ``kernels.FUSED_GP_PERIODIC = False``), [512, 8] against [100000, 8], f32; and the kernel route alone at D = 64
+periodic_gpr GPRegression over Product(Periodic, RBF), N = 4096, D = 8, f32 and f64, by the same switch
 
 Per route: milliseconds per step as the median of 5 blocks after one warm-up block, with the fastest and slowest
 block (a block is ``--iters`` steps and ends with a device synchronisation), and ``peak_mib``: the allocator's peak
@@ -51,14 +54,14 @@ def peak_mib(fn):
     return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
 
 
-def both_routes(out, step, iters):
-    for route, fused in (("kernel", True), ("torch", False)):
-        gp.kernels.FUSED_GP_KERNEL = fused
+def both_routes(out, step, iters, switch="FUSED_GP_KERNEL", routes=(("kernel", True), ("torch", False))):
+    for route, fused in routes:
+        setattr(gp.kernels, switch, fused)
         try:
             out[route + "_ms"] = blocks(step, iters)
             out[route + "_peak_mib"] = peak_mib(step)
         finally:
-            gp.kernels.FUSED_GP_KERNEL = True
+            setattr(gp.kernels, switch, True)
     print(json.dumps(out), flush=True)
 
 
@@ -115,13 +118,47 @@ def gpr(iters, dev):
         both_routes({"case": "gpr", "N": 4096, "D": 8, "dtype": str(dtype).replace("torch.", "")}, model_step(model), iters)
 
 
+def periodic(iters, dev):
+    dtype = torch.float32
+    for D, routes in ((8, (("kernel", True), ("torch", False))), (64, (("kernel", True),))):
+        X, _ = data(100000, D, dtype, dev)
+        Xu = X[::195][:512].clone().requires_grad_()
+        kern = gp.kernels.Periodic(D, lengthscale=torch.linspace(0.5, 2.0, D, dtype=dtype),
+                                   period=torch.linspace(0.7, 3.0, D, dtype=dtype)).to(dev)
+        w = torch.randn(512, 100000, dtype=dtype, device=dev)
+
+        def step():
+            Xu.grad = None
+            for p in kern.parameters():
+                p.grad = None
+            (kern(Xu, X) * w).sum().backward()
+
+        both_routes({"case": "periodic", "shape": [512, 100000, D], "dtype": "float32"}, step, iters, "FUSED_GP_PERIODIC",
+                    routes)
+
+
+def periodic_gpr(iters, dev):
+    for dtype in (torch.float32, torch.float64):
+        X, y = data(4096, 8, dtype, dev)
+        pyro.clear_param_store()
+        one = torch.ones(8, dtype=dtype)
+        kern = gp.kernels.Product(gp.kernels.Periodic(8, variance=torch.tensor(1.0, dtype=dtype), lengthscale=one.clone(),
+                                                      period=2 * one),
+                                  gp.kernels.RBF(8, variance=torch.tensor(1.0, dtype=dtype), lengthscale=one.clone())).to(dev)
+        model = gp.models.GPRegression(X, y, kern, noise=torch.tensor(0.1, dtype=dtype, device=dev),
+                                       jitter=1e-4 if dtype == torch.float32 else 1e-6)
+        both_routes({"case": "periodic_gpr", "N": 4096, "D": 8, "dtype": str(dtype).replace("torch.", "")},
+                    model_step(model), iters, "FUSED_GP_PERIODIC")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr"])
+    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr", "periodic", "periodic_gpr"])
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    for name, fn in (("covariance", covariance), ("sgpr", sgpr), ("gpr", gpr)):
+    for name, fn in (("covariance", covariance), ("sgpr", sgpr), ("gpr", gpr), ("periodic", periodic),
+                     ("periodic_gpr", periodic_gpr)):
         if args.only in (None, name):
             fn(args.iters, dev)
 
