@@ -1172,6 +1172,57 @@ int pa_gp_periodic_bwd(int dtype, const void* x, const void* z, const void* leng
                        void* gz, void* g_lengthscale, void* g_period, void* g_variance, int forced_splits,
                        void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_compose.hip: a sum of products of the kernels above in ONE covariance launch ----------------------------
+ * Replaces Sum / Product of pyro/contrib/gp/kernels/kernel.py, which evaluate every leaf into an [N, M] matrix of its
+ * own and combine them with element-wise operators that autograd keeps alive:
+ *   K[i, j] = bias + sum_t coef_t prod_{f in term t} variance_f phi_f(x_i, z_j)
+ * phi_f one of the five stationary families or PA_GP_PERIODIC, evaluated with the arithmetic of the leaf kernels on
+ * the columns cols[col0 .. col0 + D) of x and z.  The descriptor lives on the HOST and travels to the kernels by value;
+ * bias and coef are host numbers, every parameter a DEVICE pointer of the call's dtype.  Factors of term 0 come first,
+ * then those of term 1, ...; col0 is the running sum of D.  lengthscale [n_ls], n_ls = 1 or D; aux is scale_mixture
+ * [1] (n_aux = 1) for PA_GP_RATIONAL_QUADRATIC, period [n_aux] with n_aux = 1 or D for PA_GP_PERIODIC, else NULL
+ * (n_aux = 0).  Caps: PA_GP_COMPOSE_MAX_*; a descriptor outside them, or one whose LDS need exceeds a workgroup's
+ * 160 KiB, is PA_ERR_UNSUPPORTED.
+ * x [N, U], z [M, U] contiguous (z = NULL: z = x, M = N), U <= 64 the width of the union of the factors' columns.
+ * pa_gp_compose_fwd: ONE launch, K [N, M] written once.  pa_gp_compose_bwd: G [N, M]; one pass over G per side that
+ * wants a gradient gives gx [N, U] / gz [M, U] and, per factor f, the outputs of ``grads`` that are not NULL:
+ * g_variance[f] [1], g_lengthscale[f] [n_ls], g_aux[f] [n_aux].  The weight of a factor is G coef_t times the product
+ * of the OTHER factors of its term, formed by multiplication (a factor that underflows to zero divides nothing).
+ * Partial records in ``workspace`` (pa_gp_compose_bwd_workspace bytes), summed in a fixed order in float64: no
+ * atomics, bit-reproducible.  forced_splits > 0 fixes the number of column splits (tests). */
+#define PA_GP_PERIODIC 5
+#define PA_GP_COMPOSE_MAX_TERMS 6
+#define PA_GP_COMPOSE_MAX_TERM_FACTORS 3
+#define PA_GP_COMPOSE_MAX_FACTORS 8
+#define PA_GP_COMPOSE_MAX_SUM_D 256
+typedef struct pa_gp_factor {
+  const void* variance;
+  const void* lengthscale;
+  const void* aux;
+  uint8_t kind, D, n_ls, n_aux;
+  uint16_t col0, reserved;
+} pa_gp_factor;
+typedef struct pa_gp_compose_spec {
+  double bias;
+  double coef[PA_GP_COMPOSE_MAX_TERMS];
+  int32_t n_terms, n_factors, U, sum_d;
+  uint8_t term_count[8];
+  pa_gp_factor factor[PA_GP_COMPOSE_MAX_FACTORS];
+  uint8_t cols[PA_GP_COMPOSE_MAX_SUM_D];
+} pa_gp_compose_spec;
+typedef struct pa_gp_compose_grads {
+  void* g_variance[PA_GP_COMPOSE_MAX_FACTORS];
+  void* g_lengthscale[PA_GP_COMPOSE_MAX_FACTORS];
+  void* g_aux[PA_GP_COMPOSE_MAX_FACTORS];
+} pa_gp_compose_grads;
+int pa_gp_compose_fwd(int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, void* K, int64_t N,
+                      int64_t M, pa_stream_t stream);
+size_t pa_gp_compose_bwd_workspace(const pa_gp_compose_spec* spec, int64_t N, int64_t M, int z_null, int want_gx,
+                                   int want_gz, int forced_splits);
+int pa_gp_compose_bwd(int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, const void* G, int64_t N,
+                      int64_t M, void* gx, void* gz, const pa_gp_compose_grads* grads, int forced_splits,
+                      void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* ---- csrc/gp_sgpr.hip: the statistics of a sparse GP regression (DTC / VFE), streamed: Kuf [M, N] is never formed --
  * With Kuf[i, n] = k(xu_i, x_n) of the families above (same r2: direct differences, float64 up to the exponential):
  *   pa_gp_sgpr_fwd:  A [M, M] = Kuf Kuf^T (both triangles written, exactly symmetric),  b [M, Q] = Kuf r

@@ -41,6 +41,27 @@ class View2D(Structure):
 
 NULL_VIEW = View2D(None, 0, 0)
 
+
+# pa_gp_compose_spec and pa_gp_compose_grads of include/pyro_amd.h (csrc/gp_compose.hip)
+GP_COMPOSE_MAX_TERMS, GP_COMPOSE_MAX_TERM_FACTORS, GP_COMPOSE_MAX_FACTORS, GP_COMPOSE_MAX_SUM_D = 6, 3, 8, 256
+
+
+class GpFactor(Structure):
+    _fields_ = [("variance", c_void_p), ("lengthscale", c_void_p), ("aux", c_void_p), ("kind", ctypes.c_uint8),
+                ("D", ctypes.c_uint8), ("n_ls", ctypes.c_uint8), ("n_aux", ctypes.c_uint8), ("col0", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16)]
+
+
+class GpComposeSpec(Structure):
+    _fields_ = [("bias", c_double), ("coef", c_double * GP_COMPOSE_MAX_TERMS), ("n_terms", c_int32),
+                ("n_factors", c_int32), ("U", c_int32), ("sum_d", c_int32), ("term_count", ctypes.c_uint8 * 8),
+                ("factor", GpFactor * GP_COMPOSE_MAX_FACTORS), ("cols", ctypes.c_uint8 * GP_COMPOSE_MAX_SUM_D)]
+
+
+class GpComposeGrads(Structure):
+    _fields_ = [("g_variance", c_void_p * GP_COMPOSE_MAX_FACTORS), ("g_lengthscale", c_void_p * GP_COMPOSE_MAX_FACTORS),
+                ("g_aux", c_void_p * GP_COMPOSE_MAX_FACTORS)]
+
 SITE_IDENTITY = 100
 SITE_NONE = 101
 NEED_VALUE, NEED_P0, NEED_P1, VALUE_BY_CHAIN = 1, 2, 4, 16
@@ -378,6 +399,11 @@ _SIGNATURES = {
     "pa_gp_periodic_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int64, c_int64, c_int64]                                    # G N M D
                            + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),                      # grads, splits ws stream
+    "pa_gp_compose_fwd": (c_int, [c_int, POINTER(GpComposeSpec), c_void_p, c_void_p, c_void_p, c_int64, c_int64,   # .. spec x z K N M
+                                  c_void_p]),
+    "pa_gp_compose_bwd_workspace": (c_size_t, [POINTER(GpComposeSpec), c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_compose_bwd": (c_int, [c_int, POINTER(GpComposeSpec), c_void_p, c_void_p, c_void_p, c_int64, c_int64,   # .. spec x z G N M
+                                  c_void_p, c_void_p, POINTER(GpComposeGrads), c_int, c_void_p, c_size_t, c_void_p]),
     "pa_gp_sgpr_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
     "pa_gp_sgpr_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,  # .. x xu r ls n_ls var alpha
                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,                           # A b N M D Q

@@ -21,6 +21,14 @@ function and agree to the conditioning of the expansion.  ``diag=True`` never la
 or D elements each).  Its torch route is the reference's formula with [N, M, D] temporaries, ``D`` times the size of
 anything the kernel route allocates; both form the difference first, so they agree to the rounding of the angle.
 
+``Sum`` and ``Product`` evaluate their children leaf by leaf and combine the [N, M] matrices with torch operators.  With
+``FUSED_GP_COMPOSE`` on (opt-in: it saves 40-60 % of the peak memory and is faster at [4096, 4096], but was measured
+up to 25 % slower at [512, 1e5]; README, "Gaussian processes") a tree is flattened into bias + sum_t coef_t prod_f leaf_f
+-- products distributed over sums, numbers folded -- and every term whose leaves all meet the conditions of the kernel
+routes above goes into ONE launch of pa_gp_compose_fwd (csrc/gp_compose.hip: at most 6 terms, 3 factors per term, 8
+factors, a union of 64 columns), with one backward pass for all leaves; the other terms (``WhiteNoise``, ``Constant``,
+``Linear``, what exceeds the caps) are evaluated as before and added.  Fewer than two such leaves, or ``diag=True``: as before.
+
 GP training is eager: the modules close over their data, so an SVI step over them is not captured into a graph
 (``util.train``, or ``SVI(..., hip_graph=False)``), and ``torch.linalg.cholesky`` synchronises in any case.
 """
@@ -36,6 +44,7 @@ from .parameterized import Parameterized
 
 FUSED_GP_KERNEL = True            # device f32 / f64, D <= kernels.GP_KERNEL_MAX_D: pa_gp_kernel_fwd / pa_gp_kernel_bwd
 FUSED_GP_PERIODIC = True          # the same conditions for Periodic: pa_gp_periodic_fwd / pa_gp_periodic_bwd
+FUSED_GP_COMPOSE = False          # opt-in: Sum / Product trees with two or more such leaves in ONE launch (pa_gp_compose_*)
 
 
 @_dispatcher_op("gp_kernel")
@@ -106,18 +115,158 @@ class _Combination(Kernel):
     def _second(self, X, Z, diag):
         return self.kern1(X, Z, diag=diag) if isinstance(self.kern1, Kernel) else self.kern1
 
+    def forward(self, X, Z=None, diag=False):
+        if not diag and FUSED_GP_COMPOSE:
+            K = _composed(self, X, Z)
+            if K is not None:
+                return K
+        return self._plain(X, Z, diag)
+
+
+# ---- the composite route: a tree of Sum and Product as ONE sum of products -----------------------------------------
+@_dispatcher_op("gp_compose")
+class _ComposedCovariance(torch.autograd.Function):
+    """K = bias + sum_t coef_t prod_f variance_f phi_f in ONE launch (csrc/gp_compose.hip); the gradient recomputes
+    everything from the saved INPUTS (the output may be modified in place by the caller), one pass over the incoming
+    gradient per side for all the leaves.  ``params``: variance, lengthscale and (where the leaf has one) scale_mixture
+    or period of every factor, in the order of ``spec``."""
+
+    @staticmethod
+    def forward(ctx, spec, x, z, *params):
+        from ... import kernels
+        ctx.spec = spec
+        ctx.save_for_backward(x, z, *params)
+        return kernels.gp_compose_fwd(x, z, spec, _per_factor(spec, [p.reshape(-1) for p in params]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ... import kernels
+        x, z, *params = ctx.saved_tensors
+        needs = _per_factor(ctx.spec, list(ctx.needs_input_grad[3:]), False)
+        gx, gz, grads = kernels.gp_compose_bwd(x, z, ctx.spec, _per_factor(ctx.spec, [p.reshape(-1) for p in params]), g,
+                                               (ctx.needs_input_grad[1], ctx.needs_input_grad[2], needs))
+        flat = [t for (kind, _), gs in zip(_factors_of(ctx.spec), grads) for t in gs[:_n_params(kind)]]
+        return (None, gx, gz) + tuple(None if t is None else t.reshape(p.shape) for t, p in zip(flat, params))
+
+
+def _factors_of(spec):
+    return [f for _, fs in spec[1] for f in fs]
+
+
+def _n_params(kind):
+    return 3 if kind in ("rational_quadratic", "periodic") else 2
+
+
+def _per_factor(spec, flat, fill=None):
+    """The flat list (2 or 3 entries per factor) as one (variance, lengthscale, aux) per factor."""
+    out, i = [], 0
+    for kind, _ in _factors_of(spec):
+        n = _n_params(kind)
+        out.append(tuple(flat[i:i + n]) + (fill,) * (3 - n))
+        i += n
+    return out
+
+
+def _normal_form(kern):
+    """``kern`` as (terms, bias): terms a list of (coef, [leaf kernels]), products distributed over sums, numbers folded
+    into coef and bias.  A product whose expansion would exceed the caps of the composite kernel stays one opaque
+    leaf (it is then evaluated on its own, as before)."""
+    if not isinstance(kern, _Combination):
+        return [(1.0, [kern])], 0.0
+    terms0, bias0 = _normal_form(kern.kern0)
+    if isinstance(kern.kern1, Kernel):
+        terms1, bias1 = _normal_form(kern.kern1)
+    else:
+        terms1, bias1 = [], float(kern.kern1)
+    if isinstance(kern, Sum):
+        return terms0 + terms1, bias0 + bias1
+    from ... import kernels as hip
+    terms = [(c0 * c1, f0 + f1) for c0, f0 in terms0 for c1, f1 in terms1]
+    terms += [(c * bias1, f) for c, f in terms0 if bias1 != 0] + [(c * bias0, f) for c, f in terms1 if bias0 != 0]
+    if len(terms) > hip.GP_COMPOSE_MAX_TERMS or any(len(f) > hip.GP_COMPOSE_MAX_TERM_FACTORS for _, f in terms):
+        return [(1.0, [kern])], 0.0
+    return terms, bias0 * bias1
+
+
+def _leaf_parameters(leaf, X, Z):
+    """(kind, parameters) of a leaf that the composite kernel takes -- the conditions of the leaf's own kernel route,
+    without its copies of the inputs -- else None."""
+    from ... import kernels as hip
+    if isinstance(leaf, Isotropy) and leaf._family is not None and FUSED_GP_KERNEL:
+        kind, aux = leaf._family, leaf._shape_parameter()
+        sizes = (1,)
+    elif isinstance(leaf, Periodic) and FUSED_GP_PERIODIC:
+        kind, aux = "periodic", leaf.period
+        sizes = (1, len(leaf.active_dims))
+    else:
+        return None
+    variance, lengthscale, D = leaf.variance, leaf.lengthscale, len(leaf.active_dims)
+    tensors = [variance, lengthscale] + ([] if aux is None else [aux])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == X.dtype and t.dim() <= 1 for t in tensors):
+        return None
+    if (not 1 <= D <= hip.GP_KERNEL_MAX_D or variance.numel() != 1 or lengthscale.numel() not in (1, D)
+            or (aux is not None and aux.numel() not in sizes)):
+        return None
+    return kind, tensors
+
+
+def _composed(kern, X, Z):
+    """K(X, Z) of the tree under ``kern`` with every term of stationary and periodic leaves in ONE composite launch and
+    the other terms (WhiteNoise, Constant, Linear, what is over the caps) evaluated as before and added; None when
+    fewer than two leaves could share the launch, so that the tree is evaluated as before."""
+    tensors = [X] + ([] if Z is None else [Z])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == X.dtype and t.dim() == 2 for t in tensors):
+        return None
+    if X.dtype not in (torch.float32, torch.float64) or (Z is not None and Z.size(1) != X.size(1)):
+        return None
+    from ... import kernels as hip
+    terms, bias = _normal_form(kern)
+    fused, rest, cache, columns, n_factors, sum_d = [], [], {}, set(), 0, 0
+    for coef, leaves in terms:
+        for leaf in leaves:
+            if id(leaf) not in cache:
+                cache[id(leaf)] = _leaf_parameters(leaf, X, Z)
+        dims = set(d for leaf in leaves for d in leaf.active_dims)
+        size = sum(len(leaf.active_dims) for leaf in leaves)
+        if (all(cache[id(leaf)] is not None for leaf in leaves) and len(fused) < hip.GP_COMPOSE_MAX_TERMS
+                and n_factors + len(leaves) <= hip.GP_COMPOSE_MAX_FACTORS and len(columns | dims) <= hip.GP_KERNEL_MAX_D
+                and sum_d + size <= hip.GP_COMPOSE_MAX_SUM_D and max(dims) < X.size(1)):
+            fused.append((coef, leaves))
+            columns |= dims
+            n_factors, sum_d = n_factors + len(leaves), sum_d + size
+        else:
+            rest.append((coef, leaves))
+    if n_factors < 2:
+        return None
+    union = sorted(columns)
+    where = {d: i for i, d in enumerate(union)}
+    spec = (bias, tuple((coef, tuple((cache[id(leaf)][0], tuple(where[d] for d in leaf.active_dims)) for leaf in leaves))
+                        for coef, leaves in fused))
+    params = [p for _, leaves in fused for leaf in leaves for p in cache[id(leaf)][1]]
+    whole = union == list(range(X.size(1)))
+    Xs = (X if whole else X[:, union]).contiguous()
+    Zs = None if Z is None else (Z if whole else Z[:, union]).contiguous()
+    K = _ComposedCovariance.invoke(spec, Xs, Zs, *params)
+    for coef, leaves in rest:
+        term = leaves[0](X, Z)
+        for leaf in leaves[1:]:
+            term = term * leaf(X, Z)
+        K = K + (term if coef == 1.0 else coef * term)
+    return K
+
 
 class Sum(_Combination):
     """``kern0 + kern1``; the second may be a number."""
 
-    def forward(self, X, Z=None, diag=False):
+    def _plain(self, X, Z, diag):
         return self.kern0(X, Z, diag=diag) + self._second(X, Z, diag)
 
 
 class Product(_Combination):
     """``kern0 * kern1``; the second may be a number."""
 
-    def forward(self, X, Z=None, diag=False):
+    def _plain(self, X, Z, diag):
         return self.kern0(X, Z, diag=diag) * self._second(X, Z, diag)
 
 

@@ -1264,6 +1264,112 @@ def gp_periodic_bwd(x, z, lengthscale, period, variance, G, want=(True, True, Tr
     return gx, gz, g_ls, g_period, g_var
 
 
+GP_COMPOSE_KINDS = dict(GP_FAMILIES, periodic=5)
+GP_COMPOSE_MAX_TERMS, GP_COMPOSE_MAX_TERM_FACTORS = _lib.GP_COMPOSE_MAX_TERMS, _lib.GP_COMPOSE_MAX_TERM_FACTORS
+GP_COMPOSE_MAX_FACTORS, GP_COMPOSE_MAX_SUM_D = _lib.GP_COMPOSE_MAX_FACTORS, _lib.GP_COMPOSE_MAX_SUM_D
+
+
+def gp_compose_fits(spec, U):
+    """Whether ``spec`` (see gp_compose_fwd) over ``U`` staged columns is within the caps of csrc/gp_compose_plan.h."""
+    _, terms = spec
+    factors = [f for _, fs in terms for f in fs]
+    return (1 <= len(terms) <= GP_COMPOSE_MAX_TERMS and all(1 <= len(fs) <= GP_COMPOSE_MAX_TERM_FACTORS for _, fs in terms)
+            and len(factors) <= GP_COMPOSE_MAX_FACTORS and 1 <= U <= GP_KERNEL_MAX_D
+            and all(1 <= len(cols) <= GP_KERNEL_MAX_D for _, cols in factors)
+            and sum(len(cols) for _, cols in factors) <= GP_COMPOSE_MAX_SUM_D)
+
+
+def _gp_compose_args(x, z, spec, params):
+    """The descriptor pa_gp_compose_spec of ``spec`` and ``params`` (and the tensors it points into, kept alive)."""
+    bias, terms = spec
+    factors = [f for _, fs in terms for f in fs]
+    _require_gpu(x, z)
+    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_compose: x [N, U], z [M, U]"
+    U = x.shape[1]
+    if not gp_compose_fits(spec, U):
+        raise Unsupported("pyro_amd: gp_compose: %d terms, %d factors over U=%d columns are outside the caps"
+                          % (len(terms), len(factors), U))
+    assert len(params) == len(factors), "gp_compose: one (variance, lengthscale, aux) per factor"
+    d = _lib.GpComposeSpec()
+    d.bias, d.n_terms, d.n_factors, d.U = float(bias), len(terms), len(factors), U
+    for t, (coef, fs) in enumerate(terms):
+        d.coef[t], d.term_count[t] = float(coef), len(fs)
+    keep, col0 = [], 0
+    for f, ((kind, cols), (variance, lengthscale, aux)) in enumerate(zip(factors, params)):
+        kind = GP_COMPOSE_KINDS.get(kind, kind)
+        assert kind in range(6), "gp_compose: kind is 0..5 or one of %s" % sorted(GP_COMPOSE_KINDS)
+        D = len(cols)
+        n_aux = {1: (1,), 5: (1, D)}.get(kind, ())
+        _require_gpu(variance, lengthscale, aux)
+        for p in (z, variance, lengthscale, aux):
+            if p is not None and p.dtype != x.dtype:
+                raise ValueError("pyro_amd: gp_compose: one dtype throughout, got %s and %s" % (x.dtype, p.dtype))
+        if (variance.numel() != 1 or lengthscale.numel() not in (1, D) or (aux is None) != (not n_aux)
+                or (aux is not None and aux.numel() not in n_aux) or not all(0 <= c < U for c in cols)):
+            raise ValueError("pyro_amd: gp_compose: factor %d: variance of 1 element, lengthscale of 1 or D, scale_mixture "
+                             "of 1 / period of 1 or D where the kind takes one, columns inside [0, U)" % f)
+        variance, lengthscale = variance.contiguous(), lengthscale.contiguous()
+        aux = None if aux is None else aux.contiguous()
+        keep.append((variance, lengthscale, aux))
+        fa = d.factor[f]
+        fa.variance, fa.lengthscale, fa.aux = _ptr(variance), _ptr(lengthscale), _ptr(aux)
+        fa.kind, fa.D, fa.n_ls, fa.n_aux, fa.col0 = kind, D, lengthscale.numel(), 0 if aux is None else aux.numel(), col0
+        for k, c in enumerate(cols):
+            d.cols[col0 + k] = c
+        col0 += D
+    d.sum_d = col0
+    return d, x.contiguous(), None if z is None else z.contiguous(), keep
+
+
+def gp_compose_fwd(x, z, spec, params):
+    """K [N, M] = bias + sum_t coef_t prod_f variance_f phi_f(x, z): a sum of products of the stationary families and
+    the periodic kernel in ONE launch (pa_gp_compose_fwd, csrc/gp_compose.hip).  ``spec`` = (bias, terms), terms a tuple
+    of (coef, factors), a factor (kind, cols): kind one of GP_COMPOSE_KINDS, cols the columns of x / z [., U] that the
+    factor reads.  ``params``: per factor, in order, (variance [1], lengthscale [1 or D], aux) with aux the scale_mixture
+    [1], the period [1 or D] or None; device tensors of x's dtype (f32 / f64), read by the kernel.  A spec outside the
+    caps raises Unsupported; an empty result makes no launch."""
+    d, x, z, keep = _gp_compose_args(x, z, spec, params)
+    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
+    K = x.new_empty((N, M))
+    if N == 0 or M == 0:
+        return K
+    check(_lib.load().pa_gp_compose_fwd(_dtype(x), ctypes.byref(d), _ptr(x), _ptr(z), _ptr(K), N, M, _stream()))
+    return K
+
+
+def gp_compose_bwd(x, z, spec, params, G, want=None, forced_splits=0):
+    """The gradients of gp_compose_fwd's K given G = dL/dK [N, M]: (gx [N, U], gz [M, U], per factor (g_variance,
+    g_lengthscale, g_aux)), ``None`` where ``want`` = (want_gx, want_gz, per factor (variance, lengthscale, aux)) is false
+    (gz also when z is None: gx then takes both roles).  ONE pass over G per side that wants a gradient serves every
+    factor, then a fixed-order float64 finalize (pa_gp_compose_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the
+    number of column splits (tests)."""
+    d, x, z, keep = _gp_compose_args(x, z, spec, params)
+    _require_gpu(G)
+    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
+    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_compose_bwd: G [N, M] of x's dtype"
+    G = G.contiguous()
+    if want is None:
+        want = (True, True, [(True, True, True)] * len(keep))
+    want_gx, want_gz = bool(want[0]), bool(want[1]) and z is not None
+    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
+    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
+    gx = make(x) if want_gx else None
+    gz = make(z) if want_gz else None
+    grads = [tuple(make(p) if w and p is not None else None for p, w in zip(ps, ws)) for ps, ws in zip(keep, want[2])]
+    if empty or not (want_gx or want_gz or any(g is not None for gs in grads for g in gs)):
+        return gx, gz, grads
+    out = _lib.GpComposeGrads()
+    for f, (gv, gl, ga) in enumerate(grads):
+        out.g_variance[f], out.g_lengthscale[f], out.g_aux[f] = _ptr(gv), _ptr(gl), _ptr(ga)
+    lib = _lib.load()
+    nbytes = lib.pa_gp_compose_bwd_workspace(ctypes.byref(d), N, M, int(z is None), int(want_gx), int(want_gz),
+                                             int(forced_splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    check(lib.pa_gp_compose_bwd(_dtype(x), ctypes.byref(d), _ptr(x), _ptr(z), _ptr(G), N, M, _ptr(gx), _ptr(gz),
+                                ctypes.byref(out), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    return gx, gz, grads
+
+
 GP_SGPR_MAX_M = {torch.float32: 512, torch.float64: 256}      # (csrc/gp_sgpr_plan.h gps_max_m)
 GP_SGPR_MAX_Q = 16
 

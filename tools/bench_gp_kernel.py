@@ -4,7 +4,7 @@ routes of the same tree:
     torch    ``kernels.FUSED_GP_KERNEL = False``: the reference's expansion in torch operators (the baseline: the parent
              commit has no GP route at all)
 
-    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr|periodic|periodic_gpr]
+    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr|periodic|periodic_gpr|compose]
 
 covariance   K(Xu, X) forward plus backward, Matern52 with ARD lengthscales, [512, 8] against [100000, 8], f32
 sgpr         one differentiable_loss + backward of SparseGPRegression, N = 1e5, M = 512, D = 8, f32, VFE
@@ -12,6 +12,9 @@ gpr          one differentiable_loss + backward of GPRegression, N = 4096, D = 8
 periodic     K(Xu, X) forward plus backward of Periodic with ARD lengthscales and periods (csrc/gp_periodic.hip against
              ``kernels.FUSED_GP_PERIODIC = False``), [512, 8] against [100000, 8], f32; and the kernel route alone at D = 64
 periodic_gpr GPRegression over Product(Periodic, RBF), N = 4096, D = 8, f32 and f64, by the same switch
+compose      K(A, B) forward plus backward of RBF * Periodic and of the five-term Mauna Loa expression (RBF + RBF * Periodic
+             + RationalQuadratic + RBF + WhiteNoise), [512, 8] against [100000, 8] and [4096, 8] against [4096, 8], f32 and
+             f64: csrc/gp_compose.hip against ``kernels.FUSED_GP_COMPOSE = False`` (every leaf in a launch of its own)
 
 Per route: milliseconds per step as the median of 5 blocks after one warm-up block, with the fastest and slowest
 block (a block is ``--iters`` steps and ends with a device synchronisation), and ``peak_mib``: the allocator's peak
@@ -151,14 +154,40 @@ def periodic_gpr(iters, dev):
                     model_step(model), iters, "FUSED_GP_PERIODIC")
 
 
+def compose(iters, dev):
+    k = gp.kernels
+    for dtype in (torch.float32, torch.float64):
+        ls = lambda a, b: torch.linspace(a, b, 8, dtype=dtype)      # noqa: E731
+        local = lambda: k.Product(k.RBF(8, lengthscale=ls(2.0, 4.0)), k.Periodic(8, lengthscale=ls(0.5, 2.0), period=ls(0.7, 3.0)))      # noqa: E731
+        trees = {"rbf_periodic": local(),
+                 "mauna_loa": k.Sum(k.Sum(k.Sum(k.Sum(k.RBF(8, lengthscale=ls(4.0, 8.0)), local()),
+                                                k.RationalQuadratic(8, lengthscale=ls(1.0, 2.0))),
+                                          k.RBF(8, lengthscale=ls(0.3, 0.6))), k.WhiteNoise(8))}
+        for name, kern in trees.items():
+            kern = kern.to(dev, dtype)
+            for n, m in ((512, 100000), (4096, 4096)):
+                X, _ = data(max(n, m), 8, dtype, dev)
+                A, B = X[:n].clone().requires_grad_(), X[-m:].clone()
+                w = torch.randn(n, m, dtype=dtype, device=dev)
+
+                def step():
+                    A.grad = None
+                    for p in kern.parameters():
+                        p.grad = None
+                    (kern(A, B) * w).sum().backward()
+
+                both_routes({"case": "compose", "tree": name, "shape": [n, m, 8], "dtype": str(dtype).replace("torch.", "")},
+                            step, iters, "FUSED_GP_COMPOSE", (("kernel", True), ("leaves", False)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr", "periodic", "periodic_gpr"])
+    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr", "periodic", "periodic_gpr", "compose"])
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name, fn in (("covariance", covariance), ("sgpr", sgpr), ("gpr", gpr), ("periodic", periodic),
-                     ("periodic_gpr", periodic_gpr)):
+                     ("periodic_gpr", periodic_gpr), ("compose", compose)):
         if args.only in (None, name):
             fn(args.iters, dev)
 
