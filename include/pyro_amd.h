@@ -1172,6 +1172,26 @@ int pa_gp_periodic_bwd(int dtype, const void* x, const void* z, const void* leng
                        void* gz, void* g_lengthscale, void* g_period, void* g_variance, int forced_splits,
                        void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_dot.hip: the dot-product covariance matrix, on matrix cores ---------------------------------------------
+ * Replaces Polynomial of pyro/contrib/gp/kernels/dot_product.py (matmul, + bias, ** degree, * variance: four passes over
+ * [N, M]) and, on the features [X C, X sqrt(d)] with degree 1, Coregionalize of coregionalize.py:
+ *   K[i, j] = variance * (bias + sum_k x_ik z_jk)^degree
+ * x [N, D], z [M, D] contiguous (z = NULL: z = x, M = N), variance [1] and bias [1] DEVICE pointers of the call's dtype
+ * (f32 / f64); bias = NULL means 0, variance = NULL means 1.  1 <= D <= 64 and 1 <= degree <= 16, else
+ * PA_ERR_UNSUPPORTED.  s = x z^T is formed by v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64.
+ * pa_gp_dot_fwd: ONE launch that writes K once (N = 0 or M = 0: PA_OK without a launch).
+ * pa_gp_dot_bwd: G [N, M] contiguous; K is recomputed from the inputs; ONE pass over G gives the outputs that are not
+ * NULL -- gx [N, D], gz [M, D] (needs z; with z = NULL gx takes both roles), g_variance [1], g_bias [1] (each needs
+ * its parameter) -- from partial records in ``workspace`` (pa_gp_dot_bwd_workspace bytes for the same shape and flags;
+ * checked against the plan's records), summed in a fixed order in float64: no atomics, bit-reproducible.
+ * forced_splits > 0 fixes the number of column splits (tests). */
+int pa_gp_dot_fwd(int dtype, const void* x, const void* z, const void* variance, const void* bias, int degree, void* K,
+                  int64_t N, int64_t M, int64_t D, pa_stream_t stream);
+size_t pa_gp_dot_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int want_gx, int want_gz, int forced_splits);
+int pa_gp_dot_bwd(int dtype, const void* x, const void* z, const void* variance, const void* bias, int degree,
+                  const void* G, int64_t N, int64_t M, int64_t D, void* gx, void* gz, void* g_variance, void* g_bias,
+                  int forced_splits, void* workspace, size_t workspace_bytes, pa_stream_t stream);
+
 /* ---- csrc/gp_compose.hip: a sum of products of the kernels above in ONE covariance launch ----------------------------
  * Replaces Sum / Product of pyro/contrib/gp/kernels/kernel.py, which evaluate every leaf into an [N, M] matrix of its
  * own and combine them with element-wise operators that autograd keeps alive:

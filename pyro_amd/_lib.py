@@ -399,6 +399,11 @@ _SIGNATURES = {
     "pa_gp_periodic_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int64, c_int64, c_int64]                                    # G N M D
                            + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_void_p]),                      # grads, splits ws stream
+    "pa_gp_dot_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,              # .. x z var bias degree K
+                              c_int64, c_int64, c_int64, c_void_p]),                                      # N M D stream
+    "pa_gp_dot_bwd_workspace": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_dot_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64]  # .. G N M D
+                      + [c_void_p] * 4 + [c_int, c_void_p, c_size_t, c_void_p]),                          # grads, splits ws stream
     "pa_gp_compose_fwd": (c_int, [c_int, POINTER(GpComposeSpec), c_void_p, c_void_p, c_void_p, c_int64, c_int64,   # .. spec x z K N M
                                   c_void_p]),
     "pa_gp_compose_bwd_workspace": (c_size_t, [POINTER(GpComposeSpec), c_int64, c_int64, c_int, c_int, c_int, c_int]),

@@ -2,11 +2,12 @@
 regression, ``VariationalSparseGP`` with the likelihoods, ``util.conditional`` and ``util.train``.  On the device the
 stationary kernels form their covariance matrix and its gradient with csrc/gp_kernel.hip
 (``kernels.FUSED_GP_KERNEL``) and ``Periodic`` with csrc/gp_periodic.hip (``kernels.FUSED_GP_PERIODIC``); a ``Sum`` /
-``Product`` tree of them can take ONE launch of csrc/gp_compose.hip (``kernels.FUSED_GP_COMPOSE``, opt-in); sparse
-regression and the sparse variational model stream their statistics over the data (csrc/gp_sgpr.hip, csrc/gp_cond.hip).
+``Product`` tree of them can take ONE launch of csrc/gp_compose.hip (``kernels.FUSED_GP_COMPOSE``, opt-in);
+``Polynomial`` and ``Coregionalize`` form ``x . z`` on matrix cores with csrc/gp_dot.hip (``kernels.FUSED_GP_DOT``);
+sparse regression and the sparse variational model stream their statistics over the data (csrc/gp_sgpr.hip,
+csrc/gp_cond.hip).
 
-Not here: VariationalGP and GPLVM; the Cosine, Brownian, Polynomial,
-Coregionalize, Exponent, VerticalScaling and Warping kernels."""
+Not here: VariationalGP and GPLVM; the Cosine, Brownian, Exponent, VerticalScaling and Warping kernels."""
 from . import kernels, likelihoods, models, util
 from .parameterized import Parameterized
 

@@ -1,6 +1,6 @@
 """Covariance functions of Gaussian-process models (the classes and arguments of pyro/contrib/gp/kernels; the code
 is this package's): the stationary families ``RBF``, ``RationalQuadratic``, ``Exponential``, ``Matern32``,
-``Matern52`` over ``Isotropy``; ``Periodic``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``.
+``Matern52`` over ``Isotropy``; ``Periodic``; ``Polynomial`` and ``Coregionalize``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``.
 
 A stationary family has two routes, chosen in ``Isotropy.forward``.
 
@@ -20,6 +20,14 @@ function and agree to the conditioning of the expansion.  ``diag=True`` never la
 ``Periodic`` has the same two routes under ``FUSED_GP_PERIODIC`` (csrc/gp_periodic.hip; a lengthscale and a period of 1
 or D elements each).  Its torch route is the reference's formula with [N, M, D] temporaries, ``D`` times the size of
 anything the kernel route allocates; both form the difference first, so they agree to the rounding of the angle.
+
+``Polynomial`` and ``Coregionalize`` are functions of ``x . z``, which does not cancel, so their kernel route
+(``FUSED_GP_DOT``, csrc/gp_dot.hip) forms the product on matrix cores: ONE launch writes ``variance * (bias + X Z^T)^degree``
+once, the backward is one pass over the incoming gradient and nothing of size [N, M] is kept.  Conditions: those above,
+one-element ``variance`` and ``bias``, ``degree <= 16``; ``Coregionalize`` runs it on the features ``[X C, X sqrt(d)]``
+(``rank + input_dim <= 64``), which torch operators form so that autograd carries ``C`` and ``d``.  The torch route is the
+reference's formula.  ``Linear`` stays one GEMM and a scale in torch; ``Polynomial(degree=1)`` is its fused, inhomogeneous
+form.  ``Sum`` / ``Product`` and the sparse models see both classes as ordinary leaves.
 
 ``Sum`` and ``Product`` evaluate their children leaf by leaf and combine the [N, M] matrices with torch operators.  With
 ``FUSED_GP_COMPOSE`` on (opt-in: it saves 40-60 % of the peak memory and is faster at [4096, 4096], but was measured
@@ -44,6 +52,7 @@ from .parameterized import Parameterized
 
 FUSED_GP_KERNEL = True            # device f32 / f64, D <= kernels.GP_KERNEL_MAX_D: pa_gp_kernel_fwd / pa_gp_kernel_bwd
 FUSED_GP_PERIODIC = True          # the same conditions for Periodic: pa_gp_periodic_fwd / pa_gp_periodic_bwd
+FUSED_GP_DOT = True               # the same conditions for Polynomial / Coregionalize: pa_gp_dot_fwd / pa_gp_dot_bwd
 FUSED_GP_COMPOSE = False          # opt-in: Sum / Product trees with two or more such leaves in ONE launch (pa_gp_compose_*)
 
 
@@ -494,6 +503,144 @@ class WhiteNoise(Kernel):
         if Z is None:
             return self.variance.expand(X.size(0)).diag()
         return X.new_zeros(X.size(0), Z.size(0))
+
+
+# ---- kernels that are functions of x . z: the product on matrix cores -------------------------------------------------
+@_dispatcher_op("gp_dot")
+class _DotCovariance(torch.autograd.Function):
+    """K = variance * (bias + x z^T)^degree in ONE launch (csrc/gp_dot.hip; bias None: 0, variance None: 1); the gradient
+    recomputes K from the saved INPUTS (the output may be modified in place by the caller) in one pass over the incoming
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, x, z, variance, bias, degree):
+        from ... import kernels
+        ctx.degree = degree
+        ctx.save_for_backward(x, z, variance, bias)
+        flat = lambda t: None if t is None else t.reshape(-1)      # noqa: E731
+        return kernels.gp_dot_fwd(x, z, flat(variance), flat(bias), degree)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ... import kernels
+        x, z, variance, bias = ctx.saved_tensors
+        flat = lambda t: None if t is None else t.reshape(-1)      # noqa: E731
+        gx, gz, gv, gb = kernels.gp_dot_bwd(x, z, flat(variance), flat(bias), ctx.degree, g,
+                                            list(ctx.needs_input_grad[:4]))
+        return (gx, gz, None if gv is None else gv.reshape(variance.shape),
+                None if gb is None else gb.reshape(bias.shape), None)
+
+
+def _dot_inputs(kern, X, Z, parameters):
+    """The contiguous sliced inputs when the dot kernel's route applies to them and to ``parameters`` (one-element
+    tensors), else None."""
+    if not FUSED_GP_DOT:
+        return None
+    tensors = [X] + list(parameters) + ([] if Z is None else [Z])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == X.dtype for t in tensors):
+        return None
+    if X.dtype not in (torch.float32, torch.float64) or X.dim() > 2 or (Z is not None and Z.dim() > 2):
+        return None
+    if any(p.numel() != 1 for p in parameters):
+        return None
+    Xs = kern._slice_input(X)
+    Zs = None if Z is None else kern._slice_input(Z)
+    if Zs is not None and Zs.size(1) != Xs.size(1):
+        raise ValueError("Inputs must have the same number of features.")
+    return Xs, Zs
+
+
+class Polynomial(Kernel):
+    """k(x, z) = variance * (bias + x . z)^degree, ``degree`` a positive int (degree 1: the inhomogeneous linear kernel)."""
+
+    def __init__(self, input_dim, variance=None, bias=None, degree=1, active_dims=None):
+        super().__init__(input_dim, active_dims)
+        variance = torch.tensor(1.0) if variance is None else variance
+        self.variance = PyroParam(variance, constraints.positive)
+        bias = torch.tensor(1.0) if bias is None else bias
+        self.bias = PyroParam(bias, constraints.positive)
+        if not isinstance(degree, int) or degree < 1:
+            raise ValueError("Degree for Polynomial kernel should be a positive integer.")
+        self.degree = degree
+
+    def _fused(self, X, Z):
+        """The contiguous sliced inputs and the parameters when the kernel route applies, else None."""
+        from ... import kernels as hip
+        variance, bias = self.variance, self.bias
+        sliced = _dot_inputs(self, X, Z, (variance, bias))
+        if sliced is None or not 1 <= sliced[0].size(1) <= hip.GP_KERNEL_MAX_D or self.degree > hip.GP_DOT_MAX_DEGREE:
+            return None
+        Xs, Zs = sliced
+        return Xs.contiguous(), None if Zs is None else Zs.contiguous(), variance, bias, self.degree
+
+    def forward(self, X, Z=None, diag=False):
+        if diag:
+            return self.variance * (self.bias + (self._slice_input(X) ** 2).sum(-1)) ** self.degree
+        fused = self._fused(X, Z)
+        if fused is not None:
+            return _DotCovariance.invoke(*fused)
+        # the torch route: the reference's formula, four passes over [N, M]
+        X = self._slice_input(X)
+        Z = X if Z is None else self._slice_input(Z)
+        if X.size(1) != Z.size(1):
+            raise ValueError("Inputs must have the same number of features.")
+        return self.variance * (self.bias + X.matmul(Z.t())) ** self.degree
+
+
+class Coregionalize(Kernel):
+    """k(x, z) = x^T (C C^T + diag(d)) z, the linear model of coregionalization: ``components`` C [input_dim, rank] (drawn
+    with E[C C^T] = I / 2 when only ``rank``, default ``input_dim``, is given) and a positive ``diagonal`` d [input_dim]
+    (default 0.5)."""
+
+    def __init__(self, input_dim, rank=None, components=None, diagonal=None, active_dims=None):
+        super().__init__(input_dim, active_dims)
+        if components is None:
+            rank = input_dim if rank is None else rank
+            components = torch.randn(input_dim, rank) * (0.5 / rank) ** 0.5
+        else:
+            rank = components.size(-1)
+        if components.shape != (input_dim, rank):
+            raise ValueError("Expected components.shape == ({},rank), actual {}".format(input_dim, components.shape))
+        self.components = torch.nn.Parameter(components)
+        diagonal = components.new_ones(input_dim) * 0.5 if diagonal is None else diagonal
+        if diagonal.shape != (input_dim,):
+            raise ValueError("Expected diagonal.shape == ({},), actual {}".format(input_dim, diagonal.shape))
+        self.diagonal = PyroParam(diagonal, constraints.positive)
+
+    def _fused(self, X, Z):
+        """The features [X C, X sqrt(d)] of the kernel route ([N, rank + input_dim], formed by torch operators: autograd
+        carries C and d) when it applies, else None."""
+        from ... import kernels as hip
+        components, diagonal = self.components, self.diagonal
+        if not all(t.is_cuda and t.dtype == X.dtype for t in (components, diagonal)):
+            return None
+        if components.size(1) + components.size(0) > hip.GP_KERNEL_MAX_D:
+            return None
+        sliced = _dot_inputs(self, X, Z, ())
+        if sliced is None:
+            return None
+        root = diagonal.sqrt()
+        Xs, Zs = sliced
+        return (torch.cat([Xs.matmul(components), Xs * root], 1),
+                None if Zs is None else torch.cat([Zs.matmul(components), Zs * root], 1), None, None, 1)
+
+    def forward(self, X, Z=None, diag=False):
+        if not diag:
+            fused = self._fused(X, Z)
+            if fused is not None:
+                return _DotCovariance.invoke(*fused)
+        # the torch route: the reference's formula
+        X = self._slice_input(X)
+        Xc = X.matmul(self.components)
+        if diag:
+            return (Xc ** 2).sum(-1) + (X ** 2).mv(self.diagonal)
+        if Z is None:
+            Z, Zc = X, Xc
+        else:
+            Z = self._slice_input(Z)
+            Zc = Z.matmul(self.components)
+        return Xc.matmul(Zc.t()) + (X * self.diagonal).matmul(Z.t())
 
 
 class Linear(Kernel):

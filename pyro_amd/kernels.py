@@ -1264,6 +1264,72 @@ def gp_periodic_bwd(x, z, lengthscale, period, variance, G, want=(True, True, Tr
     return gx, gz, g_ls, g_period, g_var
 
 
+GP_DOT_MAX_DEGREE = 16                    # (csrc/gp_dot_plan.h GPD_MAX_DEGREE)
+GP_DOT_FLUSH = 1024                       # (GPD_FLUSH: the longest sum of gp_dot_bwd in the tensor's dtype, in columns)
+
+
+def _gp_dot_args(x, z, variance, bias, degree):
+    _require_gpu(x, z, variance, bias)
+    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_dot: x [N, D], z [M, D]"
+    assert isinstance(degree, int), "gp_dot: degree is an int"
+    D = x.shape[1]
+    if not 1 <= D <= GP_KERNEL_MAX_D or not 1 <= degree <= GP_DOT_MAX_DEGREE:
+        raise Unsupported("pyro_amd: gp_dot: D=%d outside [1, %d] or degree=%d outside [1, %d]"
+                          % (D, GP_KERNEL_MAX_D, degree, GP_DOT_MAX_DEGREE))
+    for t in (z, variance, bias):
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError("pyro_amd: gp_dot: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    if any(t is not None and t.numel() != 1 for t in (variance, bias)):
+        raise ValueError("pyro_amd: gp_dot: variance and bias have one element each")
+    return (x.contiguous(), None if z is None else z.contiguous(), None if variance is None else variance.contiguous(),
+            None if bias is None else bias.contiguous())
+
+
+def gp_dot_fwd(x, z, variance, bias, degree):
+    """K [N, M] = variance * (bias + x z^T)^degree with the product on matrix cores, ONE launch (pa_gp_dot_fwd).  x [N, D],
+    z [M, D] or None for z = x; variance and bias of one element, device tensors of x's dtype (f32 / f64) read by the
+    kernel, or None for 1 and 0.  D over GP_KERNEL_MAX_D or a degree outside [1, GP_DOT_MAX_DEGREE] raises Unsupported; an
+    empty result makes no launch."""
+    x, z, variance, bias = _gp_dot_args(x, z, variance, bias, degree)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    K = x.new_empty((N, M))
+    if N == 0 or M == 0:
+        return K
+    check(_lib.load().pa_gp_dot_fwd(_dtype(x), _ptr(x), _ptr(z), _ptr(variance), _ptr(bias), degree, _ptr(K), N, M, D,
+                                    _stream()))
+    return K
+
+
+def gp_dot_bwd(x, z, variance, bias, degree, G, want=(True, True, True, True), forced_splits=0):
+    """The gradients of gp_dot_fwd's K given G = dL/dK [N, M]: (gx, gz, g_variance, g_bias), ``None`` where ``want`` is
+    false (gz also when z is None: gx then takes both roles; g_variance and g_bias also when the parameter is None).  K
+    is recomputed from the inputs -- it is not an argument -- in ONE pass over G, then a fixed-order float64 finalize
+    (pa_gp_dot_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the number of column splits (tests)."""
+    x, z, variance, bias = _gp_dot_args(x, z, variance, bias, degree)
+    _require_gpu(G)
+    N, D = x.shape
+    M = N if z is None else z.shape[0]
+    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_dot_bwd: G [N, M] of x's dtype"
+    G = G.contiguous()
+    want_gx, want_gz, want_var, want_bias = (bool(w) for w in want)
+    want_gz, want_var, want_bias = want_gz and z is not None, want_var and variance is not None, want_bias and bias is not None
+    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
+    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
+    gx = make(x) if want_gx else None
+    gz = make(z) if want_gz else None
+    g_var = make(variance) if want_var else None
+    g_bias = make(bias) if want_bias else None
+    if empty or not (want_gx or want_gz or want_var or want_bias):
+        return gx, gz, g_var, g_bias
+    lib = _lib.load()
+    nbytes = lib.pa_gp_dot_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    check(lib.pa_gp_dot_bwd(_dtype(x), _ptr(x), _ptr(z), _ptr(variance), _ptr(bias), degree, _ptr(G), N, M, D, _ptr(gx),
+                            _ptr(gz), _ptr(g_var), _ptr(g_bias), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
+    return gx, gz, g_var, g_bias
+
+
 GP_COMPOSE_KINDS = dict(GP_FAMILIES, periodic=5)
 GP_COMPOSE_MAX_TERMS, GP_COMPOSE_MAX_TERM_FACTORS = _lib.GP_COMPOSE_MAX_TERMS, _lib.GP_COMPOSE_MAX_TERM_FACTORS
 GP_COMPOSE_MAX_FACTORS, GP_COMPOSE_MAX_SUM_D = _lib.GP_COMPOSE_MAX_FACTORS, _lib.GP_COMPOSE_MAX_SUM_D

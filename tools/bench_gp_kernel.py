@@ -4,7 +4,7 @@ routes of the same tree:
     torch    ``kernels.FUSED_GP_KERNEL = False``: the reference's expansion in torch operators (the baseline: the parent
              commit has no GP route at all)
 
-    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr|periodic|periodic_gpr|compose]
+    python tools/bench_gp_kernel.py [--iters 5] [--only covariance|sgpr|gpr|periodic|periodic_gpr|compose|dot]
 
 covariance   K(Xu, X) forward plus backward, Matern52 with ARD lengthscales, [512, 8] against [100000, 8], f32
 sgpr         one differentiable_loss + backward of SparseGPRegression, N = 1e5, M = 512, D = 8, f32, VFE
@@ -15,6 +15,9 @@ periodic_gpr GPRegression over Product(Periodic, RBF), N = 4096, D = 8, f32 and 
 compose      K(A, B) forward plus backward of RBF * Periodic and of the five-term Mauna Loa expression (RBF + RBF * Periodic
              + RationalQuadratic + RBF + WhiteNoise), [512, 8] against [100000, 8] and [4096, 8] against [4096, 8], f32 and
              f64: csrc/gp_compose.hip against ``kernels.FUSED_GP_COMPOSE = False`` (every leaf in a launch of its own)
+dot          forward plus backward of Polynomial(degree=3), [512, 8] against [100000, 8] and [4096, 8] against itself, f32
+             and f64: csrc/gp_dot.hip (``kernels.FUSED_GP_DOT = True``) against the yardstick ``variance * (bias + X @ Z.T)
+             ** degree`` written in plain torch in this file
 
 Per route: milliseconds per step as the median of 5 blocks after one warm-up block, with the fastest and slowest
 block (a block is ``--iters`` steps and ends with a device synchronisation), and ``peak_mib``: the allocator's peak
@@ -180,14 +183,46 @@ def compose(iters, dev):
                             step, iters, "FUSED_GP_COMPOSE", (("kernel", True), ("leaves", False)))
 
 
+def dot(iters, dev):
+    for dtype in (torch.float32, torch.float64):
+        for n, m in ((512, 100000), (4096, None)):
+            X, _ = data(m or n, 8, dtype, dev)
+            A, B = X[:n].clone().requires_grad_(), None if m is None else X
+            kern = gp.kernels.Polynomial(8, variance=torch.tensor(0.8, dtype=dtype), bias=torch.tensor(1.5, dtype=dtype),
+                                         degree=3).to(dev)
+            var, bias = (torch.tensor(v, dtype=dtype, device=dev, requires_grad=True) for v in (0.8, 1.5))
+            w = torch.randn(n, m or n, dtype=dtype, device=dev)
+
+            def kernel_step():
+                A.grad = None
+                for p in kern.parameters():
+                    p.grad = None
+                (kern(A, B) * w).sum().backward()
+
+            def torch_step():      # the yardstick: the expression itself, nothing of this package
+                A.grad = var.grad = bias.grad = None
+                ((var * (bias + A @ (A if B is None else B).T) ** 3) * w).sum().backward()
+
+            out = {"case": "dot", "degree": 3, "shape": [n, m or n, 8], "z": "given" if m else "x",
+                   "dtype": str(dtype).replace("torch.", "")}
+            before, gp.kernels.FUSED_GP_DOT = gp.kernels.FUSED_GP_DOT, True
+            try:
+                for route, step in (("kernel", kernel_step), ("torch", torch_step)):
+                    out[route + "_ms"] = blocks(step, iters)
+                    out[route + "_peak_mib"] = peak_mib(step)
+            finally:
+                gp.kernels.FUSED_GP_DOT = before
+            print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr", "periodic", "periodic_gpr", "compose"])
+    ap.add_argument("--only", choices=["covariance", "sgpr", "gpr", "periodic", "periodic_gpr", "compose", "dot"])
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name, fn in (("covariance", covariance), ("sgpr", sgpr), ("gpr", gpr), ("periodic", periodic),
-                     ("periodic_gpr", periodic_gpr), ("compose", compose)):
+                     ("periodic_gpr", periodic_gpr), ("compose", compose), ("dot", dot)):
         if args.only in (None, name):
             fn(args.iters, dev)
 
