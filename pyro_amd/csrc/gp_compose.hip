@@ -47,16 +47,17 @@
 // dynamic; the register table is in the README entry "Gaussian processes".
 #include "gp_compose_plan.h"
 #include "gp_families.h"
+#include "gp_host.h"
 #include "gp_periodic_dev.h"
 
 namespace pa {
 
-typedef pa_gp_compose_spec GpcSpec;
+typedef pa_gp_compose_spec GpxSpec;
 
 // the periodic factor as a family of its exponent e = sum_k s^2 / l_k^2: f = exp(-2 e); ``df`` is f itself, the
 // weight W = G K of gp_periodic.hip
 template <typename T>
-struct GpcPeriodic {
+struct GpxPeriodic {
   __device__ __forceinline__ static void eval(double e, T, T& f, T& df, T& da) {
     f = gp_exp_of<T>(-2.0 * e);
     df = f;
@@ -66,20 +67,20 @@ struct GpcPeriodic {
 
 // body(family) under a switch that is uniform over the workgroup
 template <typename T, typename F>
-__device__ __forceinline__ void gpc_with_family(int kind, F&& body) {
+__device__ __forceinline__ void gpx_with_family(int kind, F&& body) {
   switch (kind) {
     case PA_GP_RBF: body(GpRbf<T>()); break;
     case PA_GP_RATIONAL_QUADRATIC: body(GpRq<T>()); break;
     case PA_GP_EXPONENTIAL: body(GpExponential<T>()); break;
     case PA_GP_MATERN32: body(GpMatern32<T>()); break;
     case PA_GP_MATERN52: body(GpMatern52<T>()); break;
-    default: body(GpcPeriodic<T>()); break;
+    default: body(GpxPeriodic<T>()); break;
   }
 }
 
 // per factor and feature, in float64: 1 / l_k, or 1 / p_k and 1 / l_k^2, at par[2 col0 + k] and par[2 col0 + D + k]
 template <typename T>
-__device__ __forceinline__ void gpc_stage_parameters(const GpcSpec& s, double* par) {
+__device__ __forceinline__ void gpx_stage_parameters(const GpxSpec& s, double* par) {
   for (int f = 0; f < s.n_factors; ++f) {
     const pa_gp_factor& fa = s.factor[f];
     const T* ls = (const T*)fa.lengthscale;
@@ -102,7 +103,7 @@ __device__ __forceinline__ void gpc_stage_parameters(const GpcSpec& s, double* p
 // r2 (gp_kernel.hip's gp_r2_tile) or the periodic exponent sum_k s^2 / l_k^2 (gp_periodic.hip's gpp_exponent_tile) of
 // the thread's 4 x 4 entries over the factor's columns, in float64 for both dtypes
 template <typename T>
-__device__ __forceinline__ void gpc_distance_tile(const T* xs, const T* zs, const uint8_t* cols, const double* pa0, int D,
+__device__ __forceinline__ void gpx_distance_tile(const T* xs, const T* zs, const uint8_t* cols, const double* pa0, int D,
                                                   bool periodic, int stride, int ty, int tx, double (&acc)[4][4]) {
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -139,14 +140,14 @@ __device__ __forceinline__ void gpc_distance_tile(const T* xs, const T* zs, cons
 
 // v_f phi_f of the thread's 4 x 4 entries times ``into``
 template <typename T>
-__device__ __forceinline__ void gpc_multiply_factor(const GpcSpec& s, int f, const T* xs, const T* zs, const double* par,
+__device__ __forceinline__ void gpx_multiply_factor(const GpxSpec& s, int f, const T* xs, const T* zs, const double* par,
                                                     int stride, int ty, int tx, T (&into)[4][4]) {
   const pa_gp_factor& fa = s.factor[f];
   double e[4][4];
-  gpc_distance_tile(xs, zs, s.cols + fa.col0, par + 2 * fa.col0, (int)fa.D, fa.kind == PA_GP_PERIODIC, stride, ty, tx, e);
+  gpx_distance_tile(xs, zs, s.cols + fa.col0, par + 2 * fa.col0, (int)fa.D, fa.kind == PA_GP_PERIODIC, stride, ty, tx, e);
   const T var = ((const T*)fa.variance)[0];
   const T alpha = fa.kind == PA_GP_RATIONAL_QUADRATIC ? ((const T*)fa.aux)[0] : T(1);
-  gpc_with_family<T>(fa.kind, [&](auto fam) {
+  gpx_with_family<T>(fa.kind, [&](auto fam) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -160,7 +161,7 @@ __device__ __forceinline__ void gpc_multiply_factor(const GpcSpec& s, int f, con
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(GPK_THREADS) void gp_compose_fwd_kernel(const GpcSpec s, const T* __restrict__ x,
+__global__ __launch_bounds__(GPK_THREADS) void gp_compose_fwd_kernel(const GpxSpec s, const T* __restrict__ x,
                                                                      const T* __restrict__ z, T* __restrict__ K, int64_t N,
                                                                      int64_t M, int64_t col_tiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gp_lds[];
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_fwd_kernel(const GpcSp
   const int64_t i0 = rt * GPK_TILE, j0 = ct * GPK_TILE;
   gp_stage(x, i0, N, U, stride, xs);
   gp_stage(z, j0, M, U, stride, zs);
-  gpc_stage_parameters<T>(s, par);
+  gpx_stage_parameters<T>(s, par);
   __syncthreads();
   const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   T sum[4][4];
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_fwd_kernel(const GpcSp
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) prod[r][c] = (T)s.coef[t];
-    for (int fi = 0; fi < s.term_count[t]; ++fi, ++f) gpc_multiply_factor<T>(s, f, xs, zs, par, stride, ty, tx, prod);
+    for (int fi = 0; fi < s.term_count[t]; ++fi, ++f) gpx_multiply_factor<T>(s, f, xs, zs, par, stride, ty, tx, prod);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -215,20 +216,20 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_fwd_kernel(const GpcSp
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
 template <typename T>
-struct GpcBwdArgs {
+struct GpxBwdArgs {
   const T *xr, *xc;            // the points that get a gradient [R, U], the points that are walked [C, U]
   const T* G;                  // G(i, j) = G[i * g_sr + j * g_sc], one of the strides is 1
   int64_t g_sr, g_sc;
   int splits, want_rows, want_scalars;
   unsigned want_ls, want_aux;  // bit f: factor f's lengthscale / period gradient is wanted
   int64_t R, C, tiles_per_split, col_tiles;
-  double *row_rec, *sc_rec;    // [splits, R, U], [workgroups, gpc_record_doubles]
+  double *row_rec, *sc_rec;    // [splits, R, U], [workgroups, gpx_record_doubles]
 };
 
 // One factor of one term on one tile: its weight from G and the product of the others, the per-tile scalar sums, the
 // sweep over its features.  ``others``: coef_t prod_{f' != f} v_f' phi_f' of the thread's entries.
 template <typename T, bool SYM>
-__device__ __forceinline__ void gpc_factor_backward(const GpcSpec& s, const GpcBwdArgs<T>& a, int f, const T* xs, const T* zs,
+__device__ __forceinline__ void gpx_factor_backward(const GpxSpec& s, const GpxBwdArgs<T>& a, int f, const T* xs, const T* zs,
                                                     const double* par, double* acc, double* ls_acc, double* p_acc,
                                                     double* sc_acc, const T (&g)[4][4], const T (&gs)[SYM ? 4 : 1][4],
                                                     const T (&others)[4][4], int stride, int ty, int tx) {
@@ -242,8 +243,8 @@ __device__ __forceinline__ void gpc_factor_backward(const GpcSpec& s, const GpcB
   T t_var = T(0), t_alpha = T(0), t_ls = T(0);
   {
     double e[4][4];
-    gpc_distance_tile(xs, zs, cols, pa0, D, periodic, stride, ty, tx, e);
-    gpc_with_family<T>(fa.kind, [&](auto fam) {
+    gpx_distance_tile(xs, zs, cols, pa0, D, periodic, stride, ty, tx, e);
+    gpx_with_family<T>(fa.kind, [&](auto fam) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -262,7 +263,7 @@ __device__ __forceinline__ void gpc_factor_backward(const GpcSpec& s, const GpcB
   if (a.want_scalars) {
     const double v0 = wave_sum((double)t_var), v1 = wave_sum((double)t_alpha), v2 = wave_sum((double)t_ls);
     if (lane == 0) {
-      double* sc = sc_acc + (wave * GPC_MAX_FACTORS + f) * GPC_SCALARS;
+      double* sc = sc_acc + (wave * GPX_MAX_FACTORS + f) * GPX_SCALARS;
       sc[0] += v0, sc[1] += v1, sc[2] += v2;
     }
   }
@@ -318,25 +319,16 @@ __device__ __forceinline__ void gpc_factor_backward(const GpcSpec& s, const GpcB
     }
     if (a.want_rows) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const T total = gp_row16_sum(p[r]);
-        if (tx == 0) acc[(4 * ty + r) * U + col] += row_scale * (double)total;
-      }
+      for (int r = 0; r < 4; ++r) gp_row_add(p[r], row_scale, acc, (4 * ty + r) * U + col, tx);
     }
-    if (ard) {
-      const T total = wave_sum(ql);
-      if (lane == 0) ls_acc[wave * s.sum_d + fa.col0 + k] += (double)total;
-    }
-    if (want_period) {
-      const T total = wave_sum(qp);
-      if (lane == 0) p_acc[wave * s.sum_d + fa.col0 + k] += (double)total;
-    }
+    if (ard) gp_wave_add(ql, ls_acc, wave * s.sum_d + fa.col0 + k, lane);
+    if (want_period) gp_wave_add(qp, p_acc, wave * s.sum_d + fa.col0 + k, lane);
   }
 }
 
 // SYM: z = x, the row gradient's weight carries (G_ij + G_ji)
 template <typename T, bool SYM>
-__global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpcSpec s, const GpcBwdArgs<T> a) {
+__global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpxSpec s, const GpxBwdArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gp_lds[];
   const int U = s.U, stride = gpk_lds_stride(U), sum_d = s.sum_d;
   T* xs = reinterpret_cast<T*>(gp_lds);
@@ -344,15 +336,15 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpcSp
   double* par = reinterpret_cast<double*>(gp_lds + gpk_lds_head_bytes(U, sizeof(T)));      // [2 sum_d]
   double* acc = par + 2 * sum_d;                                                             // [64, U]
   double* ls_acc = acc + GPK_TILE * U;                                                       // [4, sum_d]
-  double* p_acc = ls_acc + GPC_WAVES * sum_d;                                                // [4, sum_d]
-  double* sc_acc = p_acc + GPC_WAVES * sum_d;                                                // [4, 8, 3]
+  double* p_acc = ls_acc + GPK_WAVES * sum_d;                                                // [4, sum_d]
+  double* sc_acc = p_acc + GPK_WAVES * sum_d;                                                // [4, 8, 3]
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   const int64_t rb = (int64_t)blockIdx.x / a.splits;
   const int split = (int)((int64_t)blockIdx.x - rb * a.splits);
   const int64_t i0 = rb * GPK_TILE;
   gp_stage(a.xr, i0, a.R, U, stride, xs);
-  gpc_stage_parameters<T>(s, par);
-  const int zeros = GPK_TILE * U + 2 * GPC_WAVES * sum_d + GPC_WAVES * GPC_MAX_FACTORS * GPC_SCALARS;
+  gpx_stage_parameters<T>(s, par);
+  const int zeros = GPK_TILE * U + 2 * GPK_WAVES * sum_d + GPK_WAVES * GPX_MAX_FACTORS * GPX_SCALARS;
   for (int e = tid; e < zeros; e += GPK_THREADS) acc[e] = 0.0;
   int64_t ct_end = (int64_t)(split + 1) * a.tiles_per_split;
   if (ct_end > a.col_tiles) ct_end = a.col_tiles;
@@ -386,7 +378,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpcSp
           for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int c = 0; c < 4; ++c) v2[r][c] = v1[r][c], v1[r][c] = v0[r][c], v0[r][c] = T(1);
-          gpc_multiply_factor<T>(s, f0 + fi, xs, zs, par, stride, ty, tx, v0);
+          gpx_multiply_factor<T>(s, f0 + fi, xs, zs, par, stride, ty, tx, v0);
         }
       }
       // pass 2 takes the factors from the last to the first: the current one's value sits in v0, the OTHERS are v1 and
@@ -402,30 +394,26 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpcSp
             const T front = v0[r][c];
             v0[r][c] = v1[r][c], v1[r][c] = v2[r][c], v2[r][c] = front;
           }
-        gpc_factor_backward<T, SYM>(s, a, f0 + fi, xs, zs, par, acc, ls_acc, p_acc, sc_acc, g, gs, others, stride, ty, tx);
+        gpx_factor_backward<T, SYM>(s, a, f0 + fi, xs, zs, par, acc, ls_acc, p_acc, sc_acc, g, gs, others, stride, ty, tx);
       }
       f0 += count;
     }
   }
   __syncthreads();
-  if (a.want_rows) {
-    const int64_t rows_here = a.R - i0 < GPK_TILE ? a.R - i0 : GPK_TILE;
-    double* rec = a.row_rec + ((int64_t)split * a.R + i0) * U;
-    for (int64_t e = tid; e < rows_here * U; e += GPK_THREADS) rec[e] = acc[e];
-  }
+  if (a.want_rows) gp_copy_row_record(acc, a.row_rec, split, a.R, i0, U);
   if (a.want_scalars) {
-    double* sc = a.sc_rec + (int64_t)blockIdx.x * gpc_record_doubles(s.n_factors, sum_d);
+    double* sc = a.sc_rec + (int64_t)blockIdx.x * gpx_record_doubles(s.n_factors, sum_d);
     for (int f = 0; f < s.n_factors; ++f) {
       const pa_gp_factor& fa = s.factor[f];
       const int D = fa.D;
-      double* out = sc + gpc_record_base(f, fa.col0);
-      for (int e = tid; e < GPC_SCALARS + 2 * D; e += GPK_THREADS) {
+      double* out = sc + gpx_record_base(f, fa.col0);
+      for (int e = tid; e < GPX_SCALARS + 2 * D; e += GPK_THREADS) {
         const double* src;
         int step;
-        if (e < GPC_SCALARS) src = sc_acc + f * GPC_SCALARS + e, step = GPC_MAX_FACTORS * GPC_SCALARS;
-        else if (e < GPC_SCALARS + D) src = ls_acc + fa.col0 + (e - GPC_SCALARS), step = sum_d;
-        else src = p_acc + fa.col0 + (e - GPC_SCALARS - D), step = sum_d;
-        out[e] = (src[0] + src[step]) + (src[2 * step] + src[3 * step]);
+        if (e < GPX_SCALARS) src = sc_acc + f * GPX_SCALARS + e, step = GPX_MAX_FACTORS * GPX_SCALARS;
+        else if (e < GPX_SCALARS + D) src = ls_acc + fa.col0 + (e - GPX_SCALARS), step = sum_d;
+        else src = p_acc + fa.col0 + (e - GPX_SCALARS - D), step = sum_d;
+        out[e] = gp_fold_waves(src, 0, step);
       }
     }
   }
@@ -435,7 +423,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_bwd_kernel(const GpcSp
 // i, k] (the factors' scales are in the records).  Then one block per reduced output, factor by factor: variance,
 // scale_mixture, lengthscale (n_ls of them), period (n_aux, Periodic only).
 template <typename T>
-struct GpcFinArgs {
+struct GpxFinArgs {
   const double *row_rec, *sc_rec;
   int splits;
   int64_t R, workgroups, row_fin_blocks;
@@ -443,25 +431,23 @@ struct GpcFinArgs {
   pa_gp_compose_grads g;
 };
 
-GPK_HD inline int gpc_fin_outputs(const pa_gp_factor& fa) {
+GPK_HD inline int gpx_fin_outputs(const pa_gp_factor& fa) {
   return 2 + fa.n_ls + (fa.kind == PA_GP_PERIODIC ? fa.n_aux : 0);
 }
 
 template <typename T>
-__global__ __launch_bounds__(GPK_THREADS) void gp_compose_fin_kernel(const GpcSpec s, const GpcFinArgs<T> a) {
-  __shared__ double red[GPC_WAVES];
+__global__ __launch_bounds__(GPK_THREADS) void gp_compose_fin_kernel(const GpxSpec s, const GpxFinArgs<T> a) {
+  __shared__ double red[GPK_WAVES];
   if ((int64_t)blockIdx.x < a.row_fin_blocks) {
     const int64_t e = (int64_t)blockIdx.x * GPK_THREADS + threadIdx.x, total = a.R * s.U;
     if (e >= total) return;
-    double sum = 0.0;
-    for (int sp = 0; sp < a.splits; ++sp) sum += a.row_rec[(int64_t)sp * total + e];
-    a.g_rows[e] = (T)sum;
+    a.g_rows[e] = (T)gp_sum_splits(a.row_rec, a.splits, total, e);
     return;
   }
   int which = (int)((int64_t)blockIdx.x - a.row_fin_blocks), f = 0;
-  while (f < s.n_factors - 1 && which >= gpc_fin_outputs(s.factor[f])) which -= gpc_fin_outputs(s.factor[f]), ++f;
+  while (f < s.n_factors - 1 && which >= gpx_fin_outputs(s.factor[f])) which -= gpx_fin_outputs(s.factor[f]), ++f;
   const pa_gp_factor& fa = s.factor[f];
-  const int D = fa.D, rec = gpc_record_doubles(s.n_factors, s.sum_d), base = gpc_record_base(f, fa.col0);
+  const int D = fa.D, rec = gpx_record_doubles(s.n_factors, s.sum_d), base = gpx_record_base(f, fa.col0);
   const bool periodic = fa.kind == PA_GP_PERIODIC;
   const T *ls = (const T*)fa.lengthscale, *period = (const T*)fa.aux;
   const double var = (double)((const T*)fa.variance)[0];
@@ -479,7 +465,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_fin_kernel(const GpcSp
       const int j = which - 2;
       const double l = l_of(j);
       out = a.g.g_lengthscale[f] ? (T*)a.g.g_lengthscale[f] + j : nullptr;
-      slot = fa.n_ls == 1 ? 2 : GPC_SCALARS + j;
+      slot = fa.n_ls == 1 ? 2 : GPX_SCALARS + j;
       if (periodic) scale = fa.n_ls == 1 ? 4.0 * var / l : 4.0 * var / (l * l * l);
       else scale = -2.0 * var / l;
     }
@@ -494,80 +480,67 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_compose_fin_kernel(const GpcSp
     for (int64_t w = threadIdx.x; w < a.workgroups; w += GPK_THREADS)
       for (int k = first; k < last; ++k)
         sum += 2.0 * var / ((double)period[fa.n_aux == 1 ? 0 : k] * l_of(k) * l_of(k)) *
-               a.sc_rec[w * rec + base + GPC_SCALARS + D + k];
+               a.sc_rec[w * rec + base + GPX_SCALARS + D + k];
   }
-  sum = block_sum_f64_waves(sum, red, GPC_WAVES);
+  sum = block_sum_f64_waves(sum, red, GPK_WAVES);
   if (threadIdx.x == 0) *out = (T)sum;
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
 template <typename T>
-static int gpc_fwd_launch(const GpcSpec& s, const void* x, const void* z, void* K, int64_t N, int64_t M, hipStream_t st) {
+static int gpx_fwd_launch(const GpxSpec& s, const void* x, const void* z, void* K, int64_t N, int64_t M, hipStream_t st) {
   const int64_t col_tiles = gpk_tiles(M), tiles = gpk_tiles(N) * col_tiles;
   PA_REQUIRE(tiles <= GPK_MAX_WORKGROUPS, "pa_gp_compose_fwd: %lld tiles over the grid limit", (long long)tiles);
-  const size_t lds = gpc_fwd_lds_bytes(s.U, s.sum_d, sizeof(T));
-  auto k = gp_compose_fwd_kernel<T>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(GPK_THREADS), lds, st, s, (const T*)x, (const T*)(z ? z : x), (T*)K, N, M,
-                     col_tiles);
-  return check_launch("gp_compose_fwd_kernel");
+  return gp_launch("gp_compose_fwd_kernel", gp_compose_fwd_kernel<T>, tiles, GPK_THREADS,
+                   gpx_fwd_lds_bytes(s.U, s.sum_d, sizeof(T)), st, s, (const T*)x, (const T*)(z ? z : x), (T*)K, N, M, col_tiles);
 }
 
 template <typename T>
-static int gpc_bwd_side(const GpcSpec& s, const GpkLaunchPlan& pl, const T* xr, const T* xc, const T* G, int64_t g_sr,
+static int gpx_bwd_side(const GpxSpec& s, const GpkLaunchPlan& pl, const T* xr, const T* xc, const T* G, int64_t g_sr,
                         int64_t g_sc, bool sym, const pa_gp_compose_grads& gr, bool scalars, double* ws, T* g_rows,
                         hipStream_t st) {
   PA_REQUIRE(pl.workgroups <= GPK_MAX_WORKGROUPS, "pa_gp_compose_bwd: %lld workgroups over the grid limit",
              (long long)pl.workgroups);
-  GpcBwdArgs<T> a;
+  GpxBwdArgs<T> a;
   a.xr = xr, a.xc = xc, a.G = G, a.g_sr = g_sr, a.g_sc = g_sc, a.splits = pl.splits;
   a.want_rows = pl.row_records ? 1 : 0, a.want_scalars = scalars ? 1 : 0, a.want_ls = 0, a.want_aux = 0;
   int fin_outputs = 0;
   for (int f = 0; f < s.n_factors; ++f) {
     if (gr.g_lengthscale[f]) a.want_ls |= 1u << f;
     if (gr.g_aux[f]) a.want_aux |= 1u << f;
-    fin_outputs += gpc_fin_outputs(s.factor[f]);
+    fin_outputs += gpx_fin_outputs(s.factor[f]);
   }
   a.R = pl.rows, a.C = pl.cols, a.tiles_per_split = pl.tiles_per_split, a.col_tiles = pl.col_tiles;
   a.row_rec = ws, a.sc_rec = ws + pl.row_doubles;
-  const size_t lds = gpc_bwd_lds_bytes(s.U, s.sum_d, sizeof(T));
-  auto k = sym ? gp_compose_bwd_kernel<T, true> : gp_compose_bwd_kernel<T, false>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPK_THREADS), lds, st, s, a);
-  int rc = check_launch("gp_compose_bwd_kernel");
+  int rc = gp_launch("gp_compose_bwd_kernel", sym ? gp_compose_bwd_kernel<T, true> : gp_compose_bwd_kernel<T, false>,
+                     pl.workgroups, GPK_THREADS, gpx_bwd_lds_bytes(s.U, s.sum_d, sizeof(T)), st, s, a);
   if (rc != PA_OK) return rc;
-  GpcFinArgs<T> f;
+  GpxFinArgs<T> f;
   f.row_rec = a.row_rec, f.sc_rec = a.sc_rec, f.splits = pl.splits, f.R = pl.rows, f.workgroups = pl.workgroups;
   f.row_fin_blocks = pl.row_records ? (pl.rows * s.U + GPK_THREADS - 1) / GPK_THREADS : 0;
   f.g_rows = g_rows, f.g = gr;
   const int64_t blocks = f.row_fin_blocks + (scalars ? fin_outputs : 0);
   if (blocks == 0) return PA_OK;
   PA_REQUIRE(blocks <= GPK_MAX_WORKGROUPS, "pa_gp_compose_bwd: finalize grid of %lld blocks", (long long)blocks);
-  hipLaunchKernelGGL(gp_compose_fin_kernel<T>, dim3((unsigned)blocks), dim3(GPK_THREADS), 0, st, s, f);
-  return check_launch("gp_compose_fin_kernel");
+  return gp_launch("gp_compose_fin_kernel", gp_compose_fin_kernel<T>, blocks, GPK_THREADS, 0, st, s, f);
 }
 
 template <typename T>
-static int gpc_bwd_launch(const GpcSpec& s, const GpkCallPlan& cp, const void* x, const void* z, const void* G, int64_t M,
+static int gpx_bwd_launch(const GpxSpec& s, const GpkCallPlan& cp, const void* x, const void* z, const void* G, int64_t M,
                           void* gx, void* gz, const pa_gp_compose_grads& gr, bool any_scalar, void* workspace,
                           hipStream_t st) {
-  double* ws = (double*)workspace;
-  if (cp.run_x) {
-    int rc = gpc_bwd_side<T>(s, cp.x, (const T*)x, (const T*)(z ? z : x), (const T*)G, M, 1, z == nullptr, gr, any_scalar, ws,
-                             (T*)gx, st);
-    if (rc != PA_OK) return rc;
-  }
-  if (cp.run_z)
-    return gpc_bwd_side<T>(s, cp.z, (const T*)z, (const T*)x, (const T*)G, 1, M, false, gr, any_scalar && !cp.run_x,
-                           ws + cp.z_offset_doubles, (T*)gz, st);
-  return PA_OK;
+  return gp_bwd_two_sided<T>(cp, x, z, M, gx, gz, any_scalar, workspace,
+                             [&](const GpkLaunchPlan& pl, const T* xr, const T* xc, int64_t g_sr, int64_t g_sc, bool sym,
+                                 bool scalars, double* ws, T* g_rows) {
+                               return gpx_bwd_side<T>(s, pl, xr, xc, (const T*)G, g_sr, g_sc, sym, gr, scalars, ws, g_rows, st);
+                             });
 }
 
-static int gpc_check(const char* who, int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, int64_t N,
+static int gpx_check(const char* who, int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, int64_t N,
                      int64_t M) {
   PA_REQUIRE(dtype == PA_F32 || dtype == PA_F64, "%s: dtype %d", who, dtype);
   PA_REQUIRE(spec != nullptr, "%s: null descriptor", who);
-  if (!gpc_supported(*spec, dtype == PA_F32 ? 4 : 8))
+  if (!gpx_supported(*spec, dtype == PA_F32 ? 4 : 8))
     return fail(PA_ERR_UNSUPPORTED, "%s: a descriptor of %d terms, %d factors, U=%d, sum D=%d outside the caps", who,
                 spec->n_terms, spec->n_factors, spec->U, spec->sum_d);
   PA_REQUIRE(N >= 0 && M >= 0 && N < GPK_MAX_POINTS && M < GPK_MAX_POINTS, "%s: N=%lld M=%lld", who, (long long)N,
@@ -588,20 +561,20 @@ extern "C" {
 
 int pa_gp_compose_fwd(int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, void* K, int64_t N,
                       int64_t M, pa_stream_t stream) {
-  int rc = pa::gpc_check("pa_gp_compose_fwd", dtype, spec, x, z, N, M);
+  int rc = pa::gpx_check("pa_gp_compose_fwd", dtype, spec, x, z, N, M);
   if (rc != PA_OK) return rc;
   if (N == 0 || M == 0) return PA_OK;
   PA_REQUIRE(K != nullptr, "pa_gp_compose_fwd: null output");
   hipStream_t st = pa::as_stream(stream);
-  if (dtype == PA_F32) return pa::gpc_fwd_launch<float>(*spec, x, z, K, N, M, st);
-  return pa::gpc_fwd_launch<double>(*spec, x, z, K, N, M, st);
+  if (dtype == PA_F32) return pa::gpx_fwd_launch<float>(*spec, x, z, K, N, M, st);
+  return pa::gpx_fwd_launch<double>(*spec, x, z, K, N, M, st);
 }
 
 size_t pa_gp_compose_bwd_workspace(const pa_gp_compose_spec* spec, int64_t N, int64_t M, int z_null, int want_gx,
                                    int want_gz, int forced_splits) {
-  if (spec == nullptr || !pa::gpc_spec_ok(*spec) || N <= 0 || M <= 0 || N >= pa::GPK_MAX_POINTS || M >= pa::GPK_MAX_POINTS)
+  if (spec == nullptr || !pa::gpx_spec_ok(*spec) || N <= 0 || M <= 0 || N >= pa::GPK_MAX_POINTS || M >= pa::GPK_MAX_POINTS)
     return 0;
-  return pa::gpc_call_plan(N, M, spec->U, pa::gpc_record_doubles(spec->n_factors, spec->sum_d), z_null != 0, want_gx != 0,
+  return pa::gpk_call_plan(N, M, spec->U, pa::gpx_record_doubles(spec->n_factors, spec->sum_d), z_null != 0, want_gx != 0,
                            want_gz != 0, pa::cu_count(), forced_splits)
       .bytes;
 }
@@ -609,11 +582,9 @@ size_t pa_gp_compose_bwd_workspace(const pa_gp_compose_spec* spec, int64_t N, in
 int pa_gp_compose_bwd(int dtype, const pa_gp_compose_spec* spec, const void* x, const void* z, const void* G, int64_t N,
                       int64_t M, void* gx, void* gz, const pa_gp_compose_grads* grads, int forced_splits,
                       void* workspace, size_t workspace_bytes, pa_stream_t stream) {
-  int rc = pa::gpc_check("pa_gp_compose_bwd", dtype, spec, x, z, N, M);
+  int rc = pa::gpx_check("pa_gp_compose_bwd", dtype, spec, x, z, N, M);
   if (rc != PA_OK) return rc;
   PA_REQUIRE(grads != nullptr, "pa_gp_compose_bwd: null grads");
-  PA_REQUIRE(gz == nullptr || z != nullptr, "pa_gp_compose_bwd: gz without a z (with z = x, gx takes both roles)");
-  PA_REQUIRE(forced_splits >= 0, "pa_gp_compose_bwd: forced_splits=%d", forced_splits);
   bool any_scalar = false;
   for (int f = 0; f < spec->n_factors; ++f) {
     const pa_gp_factor& fa = spec->factor[f];
@@ -621,19 +592,18 @@ int pa_gp_compose_bwd(int dtype, const pa_gp_compose_spec* spec, const void* x, 
                (int)fa.kind);
     any_scalar = any_scalar || grads->g_variance[f] || grads->g_lengthscale[f] || grads->g_aux[f];
   }
-  if (!(gx || gz || any_scalar)) return PA_OK;
-  PA_REQUIRE(N > 0 && M > 0, "pa_gp_compose_bwd: an empty matrix has zero gradients; the caller fills them");
-  PA_REQUIRE(G != nullptr, "pa_gp_compose_bwd: null G");
+  bool launch;
+  rc = pa::gp_bwd_preamble("pa_gp_compose_bwd", z, gz, forced_splits, gx || gz || any_scalar, N, M, G, &launch);
+  if (rc != PA_OK || !launch) return rc;
   const pa::GpkCallPlan cp =
-      pa::gpc_call_plan(N, M, spec->U, pa::gpc_record_doubles(spec->n_factors, spec->sum_d), z == nullptr, gx != nullptr,
+      pa::gpk_call_plan(N, M, spec->U, pa::gpx_record_doubles(spec->n_factors, spec->sum_d), z == nullptr, gx != nullptr,
                         gz != nullptr, pa::cu_count(), forced_splits);
-  // the records of BOTH launches fit the workspace that was handed in (not merely the one sized by the caller's flags)
-  PA_REQUIRE(workspace != nullptr && cp.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_compose_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, cp.bytes);
+  rc = pa::gp_workspace_check("pa_gp_compose_bwd", workspace, workspace_bytes, cp.bytes);
+  if (rc != PA_OK) return rc;
   hipStream_t st = pa::as_stream(stream);
   if (dtype == PA_F32)
-    return pa::gpc_bwd_launch<float>(*spec, cp, x, z, G, M, gx, gz, *grads, any_scalar, workspace, st);
-  return pa::gpc_bwd_launch<double>(*spec, cp, x, z, G, M, gx, gz, *grads, any_scalar, workspace, st);
+    return pa::gpx_bwd_launch<float>(*spec, cp, x, z, G, M, gx, gz, *grads, any_scalar, workspace, st);
+  return pa::gpx_bwd_launch<double>(*spec, cp, x, z, G, M, gx, gz, *grads, any_scalar, workspace, st);
 }
 
 }  // extern "C"

@@ -13,8 +13,9 @@
 // Reference path replaced: pyro/contrib/gp/util.py conditional(..., full_cov=False) as VariationalSparseGP calls it:
 // Kuf, Luu^-1 Kuf, W S and their squares, all [M, N] or larger and all kept by autograd, a dozen launches each way.
 //
-// r2 and the family functions are copies of gp_sgpr.hip's (that file and gp_kernel.hip stay untouched): the difference
-// first, its square summed in float64 up to the exponential.  The matrix primitive is gp_sgpr.hip's too, with two
+// r2 is gp_sgpr.hip's (gp_sparse_dev.h, with the wave's block and the staging) and the family functions are
+// gp_families.h's, the ones every covariance kernel evaluates: the difference first, its square summed in float64 up
+// to the exponential.  The matrix primitive (gpc_mac) is gp_sgpr.hip's gps_mac with two
 // additions: the rows of A may be clamped (the caller discards the rows past the limit) and may carry a weight.  In f32
 // it is v_mfma_f32_32x32x2_f32, in f64 the same register layout filled by VALU FMAs (v_mfma_f64_16x16x4_f64 has not
 // been tried here; whether it pays is not measured).
@@ -35,105 +36,18 @@
 // the Kuf operand as it is read from LDS, B2_j = 2 P_j^T P_j (symmetric, formed by the caller) is read as its own
 // transpose -- then a g_loc^T as Q more inner steps.  From there as gp_sgpr.hip: f' for the lane's 16 entries, float64
 // [128, D] accumulators in LDS with one writer per entry, per-chunk partials of gx, scalar records, a finalize kernel.
-#include "common.h"
 #include "gp_cond_plan.h"
+#include "gp_families.h"
+#include "gp_host.h"
+#include "gp_sparse_dev.h"
 
 namespace pa {
-
-template <typename T>
-__device__ __forceinline__ T gpc_exp(T v) {
-  if constexpr (sizeof(T) == 4) return expf(v);
-  else return exp(v);
-}
-template <typename T>
-__device__ __forceinline__ T gpc_log1p(T v) {
-  if constexpr (sizeof(T) == 4) return log1pf(v);
-  else return log1p(v);
-}
-// exp(a) for an argument held in float64; in float32 exp(hi + lo) = exp(hi) (1 + lo) (gp_kernel.hip: gp_exp_of)
-template <typename T>
-__device__ __forceinline__ T gpc_exp_of(double a) {
-  if constexpr (sizeof(T) == 8) {
-    return exp(a);
-  } else {
-    const float hi = (float)a, lo = (float)(a - (double)hi);
-    return expf(hi) * (1.0f + lo);
-  }
-}
-
-// eval(r2 in float64, alpha) -> f, df = df / d(r2), da = df / d(alpha)
-template <typename T>
-struct GpcRbf {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    f = gpc_exp_of<T>(-0.5 * r2);
-    df = T(-0.5) * f;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpcRq {
-  __device__ __forceinline__ static void eval(double r2d, T alpha, T& f, T& df, T& da) {
-    const T u = (T)r2d / (T(2) * alpha), l1 = gpc_log1p(u);
-    f = gpc_exp(-alpha * l1);
-    df = T(-0.5) * f / (T(1) + u);
-    da = f * (u / (T(1) + u) - l1);
-  }
-};
-template <typename T>
-struct GpcExponential {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double r = sqrt(r2 + 1e-12);
-    f = gpc_exp_of<T>(-r);
-    df = T(-0.5) * f / (T)r;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpcMatern32 {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double sr = 1.7320508075688772935 * sqrt(r2 + 1e-12);
-    const T e = gpc_exp_of<T>(-sr);
-    f = (T(1) + (T)sr) * e;
-    df = T(-1.5) * e;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpcMatern52 {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double r = sqrt(r2 + 1e-12), sr = 2.2360679774997896964 * r;
-    const T e = gpc_exp_of<T>(-sr);
-    f = (T(1) + (T)sr + T(5.0 / 3.0) * (T)r2) * e;
-    df = e * (T(-5.0 / 6.0) - T(5.0 * 2.2360679774997896964 / 6.0) * (T)(r2 / r));
-    da = T(0);
-  }
-};
-
-// ---- the 32 x 32 block of one wave ----------------------------------------------------------------------------------
-typedef float gpc_f32x16 __attribute__((ext_vector_type(16)));
-template <typename T>
-struct GpcAcc;
-template <>
-struct GpcAcc<float> {
-  gpc_f32x16 c;
-};
-template <>
-struct GpcAcc<double> {
-  double c[16];
-};
-template <typename T>
-__device__ __forceinline__ void gpc_clear(GpcAcc<T>& a) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) a.c[v] = T(0);
-}
-// the row of the block that register v of lane ``lane`` holds (its column is lane % 32)
-__device__ __forceinline__ int gpc_row(int v, int lane) { return 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3); }
 
 // C += diag(w) A B.  A(i, k) = A[min(i, a_rows - 1) * a_si + k * a_sk], i < 32: rows past a_rows repeat the last one and
 // the caller discards them.  WEIGHTED: w_i = w[i * w_s], else 1.  B(k, j) = B[k * b_sk + j * b_sj], read only where b_ok
 // (the lane's column j = lane % 32 exists), zero otherwise; k < K
 template <typename T, bool WEIGHTED>
-__device__ __forceinline__ void gpc_mac(GpcAcc<T>& acc, const T* A, int a_si, int a_sk, int a_rows, const T* w, int w_s,
+__device__ __forceinline__ void gpc_mac(GpsAcc<T>& acc, const T* A, int a_si, int a_sk, int a_rows, const T* w, int w_s,
                                         const T* B, int b_sk, int b_sj, int K, bool b_ok, int lane) {
   const int col = lane & 31, half = lane >> 5;
   if constexpr (sizeof(T) == 4) {
@@ -154,7 +68,7 @@ __device__ __forceinline__ void gpc_mac(GpcAcc<T>& acc, const T* A, int a_si, in
     double wi[16];
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int r = gpc_row(v, lane);
+      const int r = gps_row(v, lane);
       arow[v] = (r < a_rows ? r : a_rows - 1) * a_si;
       if constexpr (WEIGHTED) wi[v] = w[r * w_s];
     }
@@ -169,28 +83,6 @@ __device__ __forceinline__ void gpc_mac(GpcAcc<T>& acc, const T* A, int a_si, in
       }
     }
   }
-}
-
-// rows [first, first + rows) of p [n, D] into tile [rows, stride], zeros past the end
-template <typename T>
-__device__ __forceinline__ void gpc_stage(const T* __restrict__ p, int64_t first, int64_t n, int rows, int D, int stride,
-                                          T* tile) {
-  for (int e = threadIdx.x; e < rows * D; e += GPS_THREADS) {
-    const int row = e / D, k = e - row * D;
-    const int64_t i = first + row;
-    tile[row * stride + k] = i < n ? p[i * D + k] : T(0);
-  }
-}
-
-// r2 of (u, x) in float64: the difference first, then 1 / l (gp_kernel.hip: gp_r2_tile)
-template <typename T>
-__device__ __forceinline__ double gpc_r2(const T* u, const T* x, const double* inv_l, int D) {
-  double s = 0.0;
-  for (int k = 0; k < D; ++k) {
-    const double d = ((double)u[k] - (double)x[k]) * inv_l[k];
-    s = fma(d, d, s);
-  }
-  return s;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
@@ -214,7 +106,7 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_fwd_kernel(const GpcFwdAr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = tid & 31, g8 = tid >> 5;
   const int64_t n0 = (int64_t)blockIdx.x * GPS_TN;
-  gpc_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
+  gps_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
   for (int k = tid; k < D; k += GPS_THREADS) inv_l[k] = 1.0 / (double)a.ls[a.n_ls == 1 ? 0 : k];
   for (int e = tid; e < WAVES * J * GPS_TN; e += GPS_THREADS) sred[e] = 0.0;
   const T var = a.variance[0], alpha = a.alpha ? a.alpha[0] : T(1);
@@ -223,7 +115,7 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_fwd_kernel(const GpcFwdAr
   for (int i = g8; i < RB * GPS_SUB; i += 8) {
     T f = T(0), df, da;
     if (p_in && i < M) {
-      FAM<T>::eval(gpc_r2(a.xu + (int64_t)i * D, xs + p * stride, inv_l, D), alpha, f, df, da);
+      FAM<T>::eval(gps_r2(a.xu + (int64_t)i * D, xs + p * stride, inv_l, D), alpha, f, df, da);
       f *= var;
     }
     ks[i * GPS_KS + p] = f;
@@ -232,13 +124,13 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_fwd_kernel(const GpcFwdAr
   for (int t = wave; t < J * RB; t += WAVES) {      // (wave-uniform)
     const int j = t / RB, r0 = (t - j * RB) * GPS_SUB;
     const int K = (j == 0 && r0 + GPS_SUB < M) ? r0 + GPS_SUB : M;      // P_0[row, k] = 0 for k > row
-    GpcAcc<T> y;
-    gpc_clear(y);
+    GpsAcc<T> y;
+    gps_clear(y);
     gpc_mac<T, false>(y, a.Pt + (int64_t)j * M * M + r0, 1, M, M - r0, nullptr, 0, ks, GPS_KS, 1, K, true, lane);
     T ss = T(0);
 #pragma unroll
     for (int v = 0; v < 16; ++v)
-      if (r0 + gpc_row(v, lane) < M) ss += y.c[v] * y.c[v];
+      if (r0 + gps_row(v, lane) < M) ss += y.c[v] * y.c[v];
     ss += __shfl_xor(ss, 32);
     if (lane < 32) sred[(wave * J + j) * GPS_TN + lane] += (double)ss;      // this wave's own [J, 32]
   }
@@ -287,13 +179,13 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_gram_kernel(const GpcGram
   while (rem >= a.blocks - I) rem -= a.blocks - I, ++I;
   const int Jb = I + rem;
   const bool diag = I == Jb, with_b = diag && j == 0;
-  gpc_stage(a.xu, (int64_t)I * TM, a.M, TM, D, stride, xui);
-  if (!diag) gpc_stage(a.xu, (int64_t)Jb * TM, a.M, TM, D, stride, xuj);
+  gps_stage(a.xu, (int64_t)I * TM, a.M, TM, D, stride, xui);
+  if (!diag) gps_stage(a.xu, (int64_t)Jb * TM, a.M, TM, D, stride, xuj);
   for (int k = tid; k < D; k += GPS_THREADS) inv_l[k] = 1.0 / (double)a.ls[a.n_ls == 1 ? 0 : k];
   const T var = a.variance[0], alpha = a.alpha ? a.alpha[0] : T(1);
-  GpcAcc<T> acc[NT];
+  GpsAcc<T> acc[NT];
 #pragma unroll
-  for (int u = 0; u < NT; ++u) gpc_clear(acc[u]);
+  for (int u = 0; u < NT; ++u) gps_clear(acc[u]);
   double bacc[NQ];
 #pragma unroll
   for (int u = 0; u < NQ; ++u) bacc[u] = 0.0;
@@ -306,10 +198,10 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_gram_kernel(const GpcGram
       const int t = wave * NT + u, rb = t / NB, cb = t - rb * NB;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int li = rb * GPS_SUB + gpc_row(v, lane), lj = cb * GPS_SUB + (lane & 31);
+        const int li = rb * GPS_SUB + gps_row(v, lane), lj = cb * GPS_SUB + (lane & 31);
         if (li < rd && lj < rd) rec[li * rd + lj] = (flushed ? rec[li * rd + lj] : 0.0) + (double)acc[u].c[v];
       }
-      gpc_clear(acc[u]);
+      gps_clear(acc[u]);
     }
     flushed = true;
   };
@@ -321,8 +213,8 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_gram_kernel(const GpcGram
   for (int64_t s = (int64_t)split * a.steps_per_split; s < s_end; ++s) {
     const int64_t n0 = s * GPS_TN;
     __syncthreads();      // the previous step's reads of xs, rs and the Kuf tiles are over
-    gpc_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
-    if (with_b) gpc_stage(a.g_loc, n0, a.N, GPS_TN, Q, Q, rs);
+    gps_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
+    if (with_b) gps_stage(a.g_loc, n0, a.N, GPS_TN, Q, Q, rs);
     __syncthreads();
     const bool p_in = n0 + p < a.N;
     const T gw = p_in ? a.g_s[(n0 + p) * Jn + j] : T(0);
@@ -330,14 +222,14 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_gram_kernel(const GpcGram
       const int row = row0 + 8 * e;
       T ki = T(0), kj = T(0), df, da;
       if (p_in && (int64_t)I * TM + row < a.M) {
-        FAM<T>::eval(gpc_r2(xui + row * stride, xs + p * stride, inv_l, D), alpha, ki, df, da);
+        FAM<T>::eval(gps_r2(xui + row * stride, xs + p * stride, inv_l, D), alpha, ki, df, da);
         ki *= var;
       }
       ksi[row * GPS_KS + p] = ki;
       if (diag) {
         kj = ki;
       } else if (p_in && (int64_t)Jb * TM + row < a.M) {
-        FAM<T>::eval(gpc_r2(xuj + row * stride, xs + p * stride, inv_l, D), alpha, kj, df, da);
+        FAM<T>::eval(gps_r2(xuj + row * stride, xs + p * stride, inv_l, D), alpha, kj, df, da);
         kj *= var;
       }
       ksj[row * GPS_KS + p] = kj * gw;
@@ -447,15 +339,15 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_chain_kernel(const GpcCha
   for (int64_t s = (int64_t)split * a.steps_per_split; s < s_end; ++s) {
     const int64_t n0 = s * GPS_TN;
     __syncthreads();      // the previous step's reads of ks, xs, gl, gw are over
-    gpc_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
-    gpc_stage(a.g_loc, n0, a.N, GPS_TN, Q, Q, gl);
-    gpc_stage(a.g_s, n0, a.N, GPS_TN, J, J, gw);
+    gps_stage(a.x, n0, a.N, GPS_TN, D, stride, xs);
+    gps_stage(a.g_loc, n0, a.N, GPS_TN, Q, Q, gl);
+    gps_stage(a.g_s, n0, a.N, GPS_TN, J, J, gw);
     __syncthreads();
     const bool p_in = n0 + p < a.N;
     for (int jr = g8; jr < M; jr += 8) {
       T f = T(0), df, da;
       if (p_in) {
-        FAM<T>::eval(gpc_r2(a.xu + (int64_t)jr * D, xs + p * stride, inv_l, D), alpha, f, df, da);
+        FAM<T>::eval(gps_r2(a.xu + (int64_t)jr * D, xs + p * stride, inv_l, D), alpha, f, df, da);
         f *= var;
       }
       ks[jr * GPS_KS + p] = f;
@@ -464,17 +356,17 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_chain_kernel(const GpcCha
     T w[16];
     if (wave_on) {
       // G^T [32 points, 32 rows] = sum_j diag(g_s[step, j]) Kuf[:, step]^T B2_j[:, rows] + g_loc[step] a[rows]^T
-      GpcAcc<T> g;
-      gpc_clear(g);
+      GpsAcc<T> g;
+      gps_clear(g);
       for (int j = 0; j < J; ++j)
         gpc_mac<T, true>(g, ks, 1, GPS_KS, GPS_TN, gw + j, J, a.B2 + (int64_t)j * M * M + i0, M, 1, M, row_ok, lane);
       gpc_mac<T, false>(g, gl, Q, 1, GPS_TN, nullptr, 0, a.a + (int64_t)i0 * Q, 1, Q, Q, row_ok, lane);
       T t_var = T(0), t_alpha = T(0), t_ls = T(0);
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int pv = gpc_row(v, lane);
+        const int pv = gps_row(v, lane);
         const T gv = (row_ok && n0 + pv < a.N) ? g.c[v] : T(0);      // padded entries weigh nothing
-        const double r2 = gpc_r2(xu_i, xs + pv * stride, inv_l, D);
+        const double r2 = gps_r2(xu_i, xs + pv * stride, inv_l, D);
         T f, df, da;
         FAM<T>::eval(r2, alpha, f, df, da);
         w[v] = gv * var * df;
@@ -489,7 +381,7 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_chain_kernel(const GpcCha
           T sum = T(0), q2 = T(0);
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
-            const T d = (xi - xs[gpc_row(v, lane) * stride + k]) * il;
+            const T d = (xi - xs[gps_row(v, lane) * stride + k]) * il;
             sum += w[v] * d;
             q2 += w[v] * d * d;
           }
@@ -510,7 +402,7 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_chain_kernel(const GpcCha
     if (a.want_gx) {      // (uniform over the workgroup)
       __syncthreads();    // every read of Kuf[:, step] is over: the tile now carries w of the chunk's rows
 #pragma unroll
-      for (int v = 0; v < 16; ++v) ks[(wave * GPS_SUB + col) * GPS_KS + gpc_row(v, lane)] = w[v];
+      for (int v = 0; v < 16; ++v) ks[(wave * GPS_SUB + col) * GPS_KS + gps_row(v, lane)] = w[v];
       __syncthreads();
       if (p_in) {
         for (int k = g8; k < D; k += 8) {
@@ -591,11 +483,6 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_cond_chain_fin_kernel(const Gp
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
-template <typename K>
-static void gpc_allow_lds(K kernel, size_t lds) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 struct GpcIn {
   const void *x, *xu, *a, *P, *ls, *variance, *alpha, *g_loc, *g_s;      // P: Pt (forward) or B2 (backward)
   int n_ls;
@@ -608,10 +495,7 @@ static int gpc_fwd_launch(const GpcFwdPlan& pl, const GpcIn& in, void* loc, void
   a.x = (const T*)in.x, a.xu = (const T*)in.xu, a.a = (const T*)in.a, a.Pt = (const T*)in.P, a.ls = (const T*)in.ls;
   a.variance = (const T*)in.variance, a.alpha = (const T*)in.alpha, a.n_ls = in.n_ls, a.D = pl.D, a.Q = pl.Q;
   a.M = (int)in.M, a.row_blocks = pl.row_blocks, a.N = in.N, a.loc = (T*)loc, a.s = (T*)s;
-  auto k = gp_cond_fwd_kernel<T, FAM>;
-  gpc_allow_lds(k, pl.lds_bytes);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPS_THREADS), pl.lds_bytes, st, a);
-  return check_launch("gp_cond_fwd_kernel");
+  return gp_launch("gp_cond_fwd_kernel", gp_cond_fwd_kernel<T, FAM>, pl.workgroups, GPS_THREADS, pl.lds_bytes, st, a);
 }
 
 struct GpcBwdOut {
@@ -631,10 +515,7 @@ static int gpc_bwd_launch(const GpcBwdPlan& pl, const GpcIn& in, const GpcBwdOut
     a.N = N, a.M = M, a.steps = pl.steps, a.steps_per_split = pl.per_split1;
     a.a_rec = ws, a.b_rec = ws + pl.a_doubles;
     constexpr int TM = sizeof(T) == 4 ? 128 : 64;
-    auto k = gp_cond_gram_kernel<T, FAM, TM>;
-    gpc_allow_lds(k, pl.lds1_bytes);
-    hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups1), dim3(GPS_THREADS), pl.lds1_bytes, st, a);
-    rc = check_launch("gp_cond_gram_kernel");
+    rc = gp_launch("gp_cond_gram_kernel", gp_cond_gram_kernel<T, FAM, TM>, pl.workgroups1, GPS_THREADS, pl.lds1_bytes, st, a);
     if (rc != PA_OK) return rc;
     const int a_blocks = (int)gps_div_up((int64_t)pl.J * M * M, GPS_THREADS);
     const int b_blocks = (int)gps_div_up(M * pl.Q, GPS_THREADS);
@@ -654,10 +535,7 @@ static int gpc_bwd_launch(const GpcBwdPlan& pl, const GpcIn& in, const GpcBwdOut
   c.steps = pl.steps, c.steps_per_split = pl.per_split2;
   c.row_rec = ws + pl.a_doubles + pl.b_doubles, c.sc_rec = c.row_rec + pl.row_doubles;
   c.gx_rec = c.sc_rec + pl.scalar_doubles;
-  auto k = gp_cond_chain_kernel<T, FAM>;
-  gpc_allow_lds(k, pl.lds2_bytes);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups2), dim3(GPS_THREADS), pl.lds2_bytes, st, c);
-  rc = check_launch("gp_cond_chain_kernel");
+  rc = gp_launch("gp_cond_chain_kernel", gp_cond_chain_kernel<T, FAM>, pl.workgroups2, GPS_THREADS, pl.lds2_bytes, st, c);
   if (rc != PA_OK) return rc;
   GpcFinArgs<T> f;
   f.row_rec = c.row_rec, f.sc_rec = c.sc_rec, f.gx_rec = c.gx_rec, f.ls = c.ls, f.variance = c.variance, f.n_ls = in.n_ls;
@@ -671,23 +549,14 @@ static int gpc_bwd_launch(const GpcBwdPlan& pl, const GpcIn& in, const GpcBwdOut
   return check_launch("gp_cond_chain_fin_kernel");
 }
 
-#define GPC_DISPATCH(CALL, ...)                                                        \
-  switch (family) {                                                                    \
-    case PA_GP_RBF: return CALL<T, GpcRbf>(__VA_ARGS__);                               \
-    case PA_GP_RATIONAL_QUADRATIC: return CALL<T, GpcRq>(__VA_ARGS__);                 \
-    case PA_GP_EXPONENTIAL: return CALL<T, GpcExponential>(__VA_ARGS__);               \
-    case PA_GP_MATERN32: return CALL<T, GpcMatern32>(__VA_ARGS__);                     \
-    default: return CALL<T, GpcMatern52>(__VA_ARGS__);                                 \
-  }
-
 template <typename T>
 static int gpc_fwd_family(int family, const GpcFwdPlan& pl, const GpcIn& in, void* loc, void* s, hipStream_t st) {
-  GPC_DISPATCH(gpc_fwd_launch, pl, in, loc, s, st)
+  GP_FAMILY_DISPATCH(gpc_fwd_launch, pl, in, loc, s, st)
 }
 template <typename T>
 static int gpc_bwd_family(int family, const GpcBwdPlan& pl, const GpcIn& in, const GpcBwdOut& o, void* workspace,
                           hipStream_t st) {
-  GPC_DISPATCH(gpc_bwd_launch, pl, in, o, workspace, st)
+  GP_FAMILY_DISPATCH(gpc_bwd_launch, pl, in, o, workspace, st)
 }
 
 static int gpc_check(const char* who, int dtype, int family, const GpcIn& in, int64_t D, int64_t Q) {
@@ -750,8 +619,8 @@ int pa_gp_cond_bwd(int dtype, int family, const void* x, const void* xu, const v
   const size_t elem = dtype == PA_F32 ? 4 : 8;
   const pa::GpcBwdPlan pl =
       pa::gpc_bwd_plan(N, M, (int)D, (int)Q, elem, gx != nullptr, gxu != nullptr, pa::cu_count(), forced_splits);
-  PA_REQUIRE(workspace != nullptr && pl.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_cond_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, pl.bytes);
+  rc = pa::gp_workspace_check("pa_gp_cond_bwd", workspace, workspace_bytes, pl.bytes);
+  if (rc != PA_OK) return rc;
   PA_REQUIRE(pl.workgroups1 <= pa::GPS_MAX_WORKGROUPS && pl.workgroups2 <= pa::GPS_MAX_WORKGROUPS &&
                  pl.lds1_bytes <= pa::GPC_MAX_LDS && pl.lds2_bytes <= pa::GPC_MAX_LDS,
              "pa_gp_cond_bwd: inconsistent plan");

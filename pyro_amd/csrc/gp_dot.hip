@@ -35,13 +35,15 @@
 //          in turn: one writer per entry at a time) and cleared; the workgroup leaves one row record in slot ``split``.
 // gX is the rows part and gZ the cols part.  With z = x both parts run on the same G, read ONCE, and the finalize adds
 // them: gX = (W + W^T) X.  A part that no wanted gradient needs is not computed.  The finalize kernel adds the records
-// in a fixed order in float64 and rounds once.  The cols records cost ceil(N / 32) M D float64 words: for N >> M give the
-// long side the role of z.
+// in a fixed order in float64 and rounds once (the row-record copy and the sum over the splits are
+// gp_tile.h's, as in the direct-difference kernels).  The cols records cost ceil(N / 32) M D float64 words: for
+// N >> M give the long side the role of z.
 //
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage): no instantiation uses scratch; LDS is
 // dynamic; the register table is in the README entry "Gaussian processes".
-#include "common.h"
 #include "gp_dot_plan.h"
+#include "gp_host.h"
+#include "gp_tile.h"
 
 namespace pa {
 
@@ -204,7 +206,7 @@ struct GpdBwdArgs {
 template <typename T>
 __global__ __launch_bounds__(GPD_THREADS) void gp_dot_bwd_kernel(const GpdBwdArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gpd_lds[];
-  __shared__ double red[GPD_THREADS / 64];
+  __shared__ double red[GPK_WAVES];
   const int D = a.D, stride = gpd_lds_stride(D, sizeof(T)), kp = gpd_padded_d(D, sizeof(T));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
   T* xs = reinterpret_cast<T*>(gpd_lds);
@@ -295,14 +297,12 @@ __global__ __launch_bounds__(GPD_THREADS) void gp_dot_bwd_kernel(const GpdBwdArg
   if (a.rows_part) {
     __syncthreads();      // the zeros of acc are in place even where no tile was walked
     flush();
-    const int64_t r0 = rb * GPK_TILE, rows_here = a.R - r0 < GPK_TILE ? a.R - r0 : GPK_TILE;
-    double* rec = a.row_rec + ((int64_t)split * a.R + r0) * D;
-    for (int64_t e = tid; e < rows_here * D; e += GPD_THREADS) rec[e] = acc[e];
+    gp_copy_row_record(acc, a.row_rec, split, a.R, rb * GPK_TILE, D);
   }
   if (a.want_scalars) {
     double* sc = a.sc_rec + (int64_t)blockIdx.x * GPD_SCALARS;
-    const double v0 = block_sum_f64_waves(s_var, red, GPD_THREADS / 64);
-    const double v1 = block_sum_f64_waves(s_bias, red, GPD_THREADS / 64);
+    const double v0 = block_sum_f64_waves(s_var, red, GPK_WAVES);
+    const double v1 = block_sum_f64_waves(s_bias, red, GPK_WAVES);
     if (tid == 0) sc[0] = v0, sc[1] = v1;
   }
 }
@@ -320,14 +320,13 @@ struct GpdFinArgs {
 
 template <typename T>
 __global__ __launch_bounds__(GPD_THREADS) void gp_dot_fin_kernel(const GpdFinArgs<T> a) {
-  __shared__ double red[GPD_THREADS / 64];
+  __shared__ double red[GPK_WAVES];
   const int64_t blk = blockIdx.x;
   if (blk < a.x_blocks) {
     const int64_t e = blk * GPD_THREADS + threadIdx.x, total = a.R * a.D;
     if (e >= total) return;
     double s = 0.0;
-    if (a.rows_part)
-      for (int sp = 0; sp < a.splits; ++sp) s += a.row_rec[(int64_t)sp * total + e];
+    if (a.rows_part) s = gp_sum_splits(a.row_rec, a.splits, total, e);
     if (a.sym)
       for (int64_t h = 0; h < a.half_blocks; ++h) s += a.col_rec[h * total + e];
     a.gx[e] = (T)s;
@@ -346,7 +345,7 @@ __global__ __launch_bounds__(GPD_THREADS) void gp_dot_fin_kernel(const GpdFinArg
   if (out == nullptr) return;      // (uniform over the block)
   double s = 0.0;
   for (int64_t w = threadIdx.x; w < a.workgroups; w += GPD_THREADS) s += a.sc_rec[w * GPD_SCALARS + slot];
-  s = block_sum_f64_waves(s, red, GPD_THREADS / 64);
+  s = block_sum_f64_waves(s, red, GPK_WAVES);
   if (threadIdx.x == 0) *out = (T)s;
 }
 
@@ -356,12 +355,8 @@ static int gpd_fwd_launch(const void* x, const void* z, const void* variance, co
                           int64_t N, int64_t M, int D, hipStream_t st) {
   const int64_t col_tiles = gpk_tiles(M), tiles = gpk_tiles(N) * col_tiles;
   PA_REQUIRE(tiles <= GPK_MAX_WORKGROUPS, "pa_gp_dot_fwd: %lld tiles over the grid limit", (long long)tiles);
-  const size_t lds = gpd_fwd_lds_bytes(D, sizeof(T));
-  auto k = gp_dot_fwd_kernel<T>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(GPD_THREADS), lds, st, (const T*)x, (const T*)(z ? z : x),
-                     (const T*)variance, (const T*)bias, degree, (T*)K, N, M, D, col_tiles);
-  return check_launch("gp_dot_fwd_kernel");
+  return gp_launch("gp_dot_fwd_kernel", gp_dot_fwd_kernel<T>, tiles, GPD_THREADS, gpd_fwd_lds_bytes(D, sizeof(T)), st,
+                   (const T*)x, (const T*)(z ? z : x), (const T*)variance, (const T*)bias, degree, (T*)K, N, M, D, col_tiles);
 }
 
 struct GpdOut {
@@ -381,11 +376,8 @@ static int gpd_bwd_launch(const GpdPlan& pl, const void* x, const void* z, const
   a.cols_part = pl.cols_part ? 1 : 0, a.want_scalars = scalars ? 1 : 0, a.R = g.rows, a.C = g.cols;
   a.tiles_per_split = g.tiles_per_split, a.col_tiles = g.col_tiles, a.half_blocks = pl.half_blocks;
   a.row_rec = (double*)workspace, a.col_rec = a.row_rec + pl.row_doubles, a.sc_rec = a.col_rec + pl.col_doubles;
-  const size_t lds = gpd_bwd_lds_bytes(g.D, sizeof(T));
-  auto k = gp_dot_bwd_kernel<T>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)g.workgroups), dim3(GPD_THREADS), lds, st, a);
-  int rc = check_launch("gp_dot_bwd_kernel");
+  int rc = gp_launch("gp_dot_bwd_kernel", gp_dot_bwd_kernel<T>, g.workgroups, GPD_THREADS, gpd_bwd_lds_bytes(g.D, sizeof(T)),
+                     st, a);
   if (rc != PA_OK) return rc;
   GpdFinArgs<T> f;
   f.row_rec = a.row_rec, f.col_rec = a.col_rec, f.sc_rec = a.sc_rec, f.D = g.D, f.splits = g.splits;
@@ -396,8 +388,7 @@ static int gpd_bwd_launch(const GpdPlan& pl, const void* x, const void* z, const
   f.gx = (T*)o.gx, f.gz = (T*)o.gz, f.g_var = (T*)o.g_var, f.g_bias = (T*)o.g_bias;
   const int64_t blocks = f.x_blocks + f.z_blocks + (scalars ? GPD_SCALARS : 0);
   PA_REQUIRE(blocks <= GPK_MAX_WORKGROUPS, "pa_gp_dot_bwd: finalize grid of %lld blocks", (long long)blocks);
-  hipLaunchKernelGGL(gp_dot_fin_kernel<T>, dim3((unsigned)blocks), dim3(GPD_THREADS), 0, st, f);
-  return check_launch("gp_dot_fin_kernel");
+  return gp_launch("gp_dot_fin_kernel", gp_dot_fin_kernel<T>, blocks, GPD_THREADS, 0, st, f);
 }
 
 static int gpd_check(const char* who, int dtype, const void* x, const void* z, int degree, int64_t N, int64_t M,
@@ -437,16 +428,14 @@ int pa_gp_dot_bwd(int dtype, const void* x, const void* z, const void* variance,
                   int forced_splits, void* workspace, size_t workspace_bytes, pa_stream_t stream) {
   int rc = pa::gpd_check("pa_gp_dot_bwd", dtype, x, z, degree, N, M, D);
   if (rc != PA_OK) return rc;
-  PA_REQUIRE(gz == nullptr || z != nullptr, "pa_gp_dot_bwd: gz without a z (with z = x, gx takes both roles)");
   PA_REQUIRE((g_variance == nullptr || variance != nullptr) && (g_bias == nullptr || bias != nullptr),
              "pa_gp_dot_bwd: a gradient for a parameter that was not given");
-  PA_REQUIRE(forced_splits >= 0, "pa_gp_dot_bwd: forced_splits=%d", forced_splits);
-  if (!(gx || gz || g_variance || g_bias)) return PA_OK;
-  PA_REQUIRE(N > 0 && M > 0, "pa_gp_dot_bwd: an empty matrix has zero gradients; the caller fills them");
-  PA_REQUIRE(G != nullptr, "pa_gp_dot_bwd: null G");
+  bool launch;
+  rc = pa::gp_bwd_preamble("pa_gp_dot_bwd", z, gz, forced_splits, gx || gz || g_variance || g_bias, N, M, G, &launch);
+  if (rc != PA_OK || !launch) return rc;
   const pa::GpdPlan pl = pa::gpd_plan(N, M, (int)D, z == nullptr, gx != nullptr, gz != nullptr, pa::cu_count(), forced_splits);
-  PA_REQUIRE(workspace != nullptr && pl.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_dot_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, pl.bytes);
+  rc = pa::gp_workspace_check("pa_gp_dot_bwd", workspace, workspace_bytes, pl.bytes);
+  if (rc != PA_OK) return rc;
   PA_REQUIRE((pl.row_doubles + pl.col_doubles + pl.scalar_doubles) * sizeof(double) == pl.bytes &&
                  pl.half_blocks * pa::GPD_SUB >= N && pl.grid.row_blocks * 2 >= pl.half_blocks,
              "pa_gp_dot_bwd: inconsistent plan");

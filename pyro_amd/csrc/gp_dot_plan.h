@@ -29,7 +29,7 @@ GPK_HD inline int gpd_lds_stride(int D, size_t elem) { return gpk_lds_stride(gpd
 GPK_HD inline size_t gpd_fwd_lds_bytes(int D, size_t elem) { return (size_t)2 * GPK_TILE * gpd_lds_stride(D, elem) * elem; }
 // backward: the tiles, one [32, 33] transposition buffer per wave, then (8-byte aligned) the float64 rows [TILE, D]
 GPK_HD inline size_t gpd_bwd_acc_offset(int D, size_t elem) {
-  return (gpd_fwd_lds_bytes(D, elem) + (size_t)(GPD_THREADS / 64) * GPD_SUB * GPD_WT * elem + 7) / 8 * 8;
+  return (gpd_fwd_lds_bytes(D, elem) + (size_t)GPK_WAVES * GPD_SUB * GPD_WT * elem + 7) / 8 * 8;
 }
 inline size_t gpd_bwd_lds_bytes(int D, size_t elem) { return gpd_bwd_acc_offset(D, elem) + (size_t)GPK_TILE * D * sizeof(double); }
 
@@ -48,7 +48,7 @@ inline GpdPlan gpd_plan(int64_t N, int64_t M, int D, bool z_null, bool want_gx, 
   p.sym = z_null;
   p.rows_part = want_gx;
   p.cols_part = z_null ? want_gx : want_gz;
-  p.grid = gpk_launch_plan(N, z_null ? N : M, D, p.rows_part, cus, forced_splits);
+  p.grid = gpk_launch_plan(N, z_null ? N : M, D, GPD_SCALARS, p.rows_part, cus, forced_splits);
   p.half_blocks = (N + GPD_SUB - 1) / GPD_SUB;
   p.row_doubles = p.grid.row_doubles;
   p.col_doubles = p.cols_part ? (size_t)p.half_blocks * (size_t)p.grid.cols * (size_t)D : 0;

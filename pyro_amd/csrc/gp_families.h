@@ -1,9 +1,24 @@
-// gp_families.h -- the five stationary families as device evaluators, shared by the leaf kernel (gp_kernel.hip) and the
-// composite kernel (gp_compose.hip): f(r2) and f'(r2) = df / d(r2), the reference's guard r = sqrt(r2 + 1e-12) inside.
+// gp_families.h -- the five stationary families as device evaluators, the ONE copy that every Gaussian-process kernel
+// evaluates (gp_kernel.hip, gp_compose.hip, gp_sgpr.hip, gp_cond.hip): f(r2) and f'(r2) = df / d(r2), the reference's
+// guard r = sqrt(r2 + 1e-12) inside, the exponential of a float64 argument (gp_exp_of, which gp_periodic.hip takes as
+// well) and the switch over the family.  The guard and the hi / lo exponential are numerics that the tests' bounds were
+// derived with: they live here and nowhere else.  Stands on common.h alone, no tile geometry.
 #pragma once
-#include "gp_tile.h"
+#include "common.h"
 
 namespace pa {
+
+// exp(a) for an argument held in float64.  In float32 the argument is split into its rounded value and the remainder,
+// exp(hi + lo) = exp(hi) (1 + lo): rounding a = -r2 / 2 to float32 alone would cost |a| 2^-24 relative (4e-6 at r2 = 130).
+template <typename T>
+__device__ __forceinline__ T gp_exp_of(double a) {
+  if constexpr (sizeof(T) == 8) {
+    return exp(a);
+  } else {
+    const float hi = (float)a, lo = (float)(a - (double)hi);
+    return expf(hi) * (1.0f + lo);
+  }
+}
 
 // ---- the families: f(r2) and f'(r2) = df / d(r2), the guard inside --------------------------------------------------
 template <typename T>
@@ -69,5 +84,15 @@ struct GpMatern52 {
     da = T(0);
   }
 };
+
+// CALL<T, family>(...) under the switch over ``family`` (PA_GP_RBF .. PA_GP_MATERN52, checked by the caller)
+#define GP_FAMILY_DISPATCH(CALL, ...)                                                 \
+  switch (family) {                                                                   \
+    case PA_GP_RBF: return CALL<T, GpRbf>(__VA_ARGS__);                               \
+    case PA_GP_RATIONAL_QUADRATIC: return CALL<T, GpRq>(__VA_ARGS__);                 \
+    case PA_GP_EXPONENTIAL: return CALL<T, GpExponential>(__VA_ARGS__);               \
+    case PA_GP_MATERN32: return CALL<T, GpMatern32>(__VA_ARGS__);                     \
+    default: return CALL<T, GpMatern52>(__VA_ARGS__);                                 \
+  }
 
 }  // namespace pa

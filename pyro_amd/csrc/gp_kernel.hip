@@ -32,10 +32,16 @@
 // the same kernel with the roles of x and z exchanged (G read through transposed strides).  With z = x (null) one
 // launch gives x both roles: the weight of the row gradient is (G_ij + G_ji) f', G is read twice.
 //
+// Shared with gp_periodic.hip and gp_compose.hip, one copy each: the frame of the tile (gp_tile.h: staging, the load
+// of G, the one-writer adds, the four-wave fold, the record copy, the finalize's
+// sum over the splits), the families (gp_families.h) and the host side (gp_host.h: launch, two-sided driver, checks).
+//
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage): no instantiation uses scratch; LDS is
 // dynamic (gp_kernel_plan.h); forward 62 (f32) / 80 (f64) VGPRs, 8 / 6 waves per SIMD; backward 186-214 (f32, 2
 // waves) and 255-256 with up to 100 AGPRs (f64, 2 or 1 waves); the table is in the README entry "Gaussian processes".
 #include "gp_families.h"
+#include "gp_host.h"
+#include "gp_tile.h"
 
 namespace pa {
 
@@ -136,7 +142,7 @@ struct GpBwdArgs {
 template <typename T, template <typename> class FAM>
 __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_bwd_kernel(const GpBwdArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gp_lds[];
-  __shared__ double red[GPK_THREADS / 64];
+  __shared__ double red[GPK_WAVES];
   const int D = a.D, stride = gpk_lds_stride(D);
   T* xs = reinterpret_cast<T*>(gp_lds);
   T* zs = xs + GPK_TILE * stride;
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_bwd_kernel(const GpBwdA
   const int64_t i0 = rb * GPK_TILE;
   gp_stage(a.xr, i0, a.R, D, stride, xs);
   gp_inverse_lengthscale(a.ls, a.n_ls, D, inv_l);
-  for (int e = tid; e < GPK_TILE * D + (GPK_THREADS / 64) * D; e += GPK_THREADS) acc[e] = 0.0;
+  for (int e = tid; e < GPK_TILE * D + GPK_WAVES * D; e += GPK_THREADS) acc[e] = 0.0;
   const T alpha = a.alpha ? a.alpha[0] : T(1);
   const bool ard = a.want_ls && a.n_ls != 1;
   double s_var = 0.0, s_alpha = 0.0, s_ls = 0.0;
@@ -200,33 +206,22 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_bwd_kernel(const GpBwdA
         }
         if (a.want_rows) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const T total = gp_row16_sum(p[r]);
-            if (tx == 0) acc[(4 * ty + r) * D + k] += (double)total;
-          }
+          for (int r = 0; r < 4; ++r) gp_row_add(p[r], acc, (4 * ty + r) * D + k, tx);
         }
-        if (ard) {
-          const T total = wave_sum(q);
-          if (lane == 0) ls_acc[wave * D + k] += (double)total;
-        }
+        if (ard) gp_wave_add(q, ls_acc, wave * D + k, lane);
       }
     }
   }
   __syncthreads();
-  if (a.want_rows) {
-    const int64_t rows_here = a.R - i0 < GPK_TILE ? a.R - i0 : GPK_TILE;
-    double* rec = a.row_rec + ((int64_t)split * a.R + i0) * D;
-    for (int64_t e = tid; e < rows_here * D; e += GPK_THREADS) rec[e] = acc[e];
-  }
-  double* sc = a.sc_rec + (int64_t)blockIdx.x * (GPK_SCALARS + D);
+  if (a.want_rows) gp_copy_row_record(acc, a.row_rec, split, a.R, i0, D);
+  double* sc = a.sc_rec + (int64_t)blockIdx.x * gpk_record_doubles(D);
   if (a.want_scalars) {
-    const double v0 = block_sum_f64_waves(s_var, red, GPK_THREADS / 64);
-    const double v1 = block_sum_f64_waves(s_alpha, red, GPK_THREADS / 64);
-    const double v2 = block_sum_f64_waves(s_ls, red, GPK_THREADS / 64);
+    const double v0 = block_sum_f64_waves(s_var, red, GPK_WAVES);
+    const double v1 = block_sum_f64_waves(s_alpha, red, GPK_WAVES);
+    const double v2 = block_sum_f64_waves(s_ls, red, GPK_WAVES);
     if (tid == 0) sc[0] = v0, sc[1] = v1, sc[2] = v2;
     if (ard)
-      for (int k = tid; k < D; k += GPK_THREADS)
-        sc[GPK_SCALARS + k] = (ls_acc[k] + ls_acc[D + k]) + (ls_acc[2 * D + k] + ls_acc[3 * D + k]);
+      for (int k = tid; k < D; k += GPK_THREADS) sc[GPK_SCALARS + k] = gp_fold_waves(ls_acc, k, D);
   }
 }
 
@@ -243,14 +238,13 @@ struct GpFinArgs {
 
 template <typename T>
 __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_fin_kernel(const GpFinArgs<T> a) {
-  __shared__ double red[GPK_THREADS / 64];
+  __shared__ double red[GPK_WAVES];
   const double var = (double)a.variance[0];
   if ((int64_t)blockIdx.x < a.row_fin_blocks) {
     const int64_t e = (int64_t)blockIdx.x * GPK_THREADS + threadIdx.x, total = a.R * a.D;
     if (e >= total) return;
     const int k = (int)(e % a.D);
-    double s = 0.0;
-    for (int sp = 0; sp < a.splits; ++sp) s += a.row_rec[(int64_t)sp * total + e];
+    const double s = gp_sum_splits(a.row_rec, a.splits, total, e);
     a.g_rows[e] = (T)(2.0 * var / (double)a.ls[a.n_ls == 1 ? 0 : k] * s);
     return;
   }
@@ -262,8 +256,8 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_fin_kernel(const GpFinA
   else slot = 1, out = a.g_alpha;
   if (out == nullptr) return;                     // (uniform over the block)
   double s = 0.0;
-  for (int64_t w = threadIdx.x; w < a.workgroups; w += GPK_THREADS) s += a.sc_rec[w * (GPK_SCALARS + a.D) + slot];
-  s = block_sum_f64_waves(s, red, GPK_THREADS / 64);
+  for (int64_t w = threadIdx.x; w < a.workgroups; w += GPK_THREADS) s += a.sc_rec[w * gpk_record_doubles(a.D) + slot];
+  s = block_sum_f64_waves(s, red, GPK_WAVES);
   if (threadIdx.x == 0) {
     if (which < a.n_ls) s *= -2.0 * var / (double)a.ls[which];
     else if (which > a.n_ls) s *= var;
@@ -277,12 +271,9 @@ static int gp_fwd_launch(const void* x, const void* z, const void* ls, int n_ls,
                          void* K, int64_t N, int64_t M, int D, hipStream_t st) {
   const int64_t col_tiles = gpk_tiles(M), tiles = gpk_tiles(N) * col_tiles;
   PA_REQUIRE(tiles <= GPK_MAX_WORKGROUPS, "pa_gp_kernel_fwd: %lld tiles over the grid limit", (long long)tiles);
-  const size_t lds = gpk_fwd_lds_bytes(D, sizeof(T));
-  auto k = gp_kernel_fwd_kernel<T, FAM>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(GPK_THREADS), lds, st, (const T*)x, (const T*)(z ? z : x), (const T*)ls,
-                     n_ls, (const T*)variance, (const T*)alpha, (T*)K, N, M, D, col_tiles);
-  return check_launch("gp_kernel_fwd_kernel");
+  return gp_launch("gp_kernel_fwd_kernel", gp_kernel_fwd_kernel<T, FAM>, tiles, GPK_THREADS, gpk_fwd_lds_bytes(D, sizeof(T)),
+                   st, (const T*)x, (const T*)(z ? z : x), (const T*)ls, n_ls, (const T*)variance, (const T*)alpha, (T*)K, N,
+                   M, D, col_tiles);
 }
 
 template <typename T, template <typename> class FAM>
@@ -297,11 +288,8 @@ static int gp_bwd_side(const GpkLaunchPlan& pl, const T* xr, const T* xc, const 
   a.want_rows = pl.row_records ? 1 : 0, a.want_ls = want_ls && scalars ? 1 : 0, a.want_scalars = scalars ? 1 : 0;
   a.R = pl.rows, a.C = pl.cols, a.tiles_per_split = pl.tiles_per_split, a.col_tiles = pl.col_tiles;
   a.row_rec = ws, a.sc_rec = ws + pl.row_doubles;
-  const size_t lds = gpk_bwd_lds_bytes(pl.D, sizeof(T));
-  auto k = gp_kernel_bwd_kernel<T, FAM>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPK_THREADS), lds, st, a);
-  int rc = check_launch("gp_kernel_bwd_kernel");
+  int rc = gp_launch("gp_kernel_bwd_kernel", gp_kernel_bwd_kernel<T, FAM>, pl.workgroups, GPK_THREADS,
+                     gpk_bwd_lds_bytes(pl.D, sizeof(T)), st, a);
   if (rc != PA_OK) return rc;
   GpFinArgs<T> f;
   f.row_rec = a.row_rec, f.sc_rec = a.sc_rec, f.ls = ls, f.variance = variance, f.n_ls = n_ls, f.D = pl.D;
@@ -311,51 +299,33 @@ static int gp_bwd_side(const GpkLaunchPlan& pl, const T* xr, const T* xc, const 
   const int64_t blocks = f.row_fin_blocks + (scalars ? n_ls + 2 : 0);
   if (blocks == 0) return PA_OK;
   PA_REQUIRE(blocks <= GPK_MAX_WORKGROUPS, "pa_gp_kernel_bwd: finalize grid of %lld blocks", (long long)blocks);
-  hipLaunchKernelGGL(gp_kernel_fin_kernel<T>, dim3((unsigned)blocks), dim3(GPK_THREADS), 0, st, f);
-  return check_launch("gp_kernel_fin_kernel");
+  return gp_launch("gp_kernel_fin_kernel", gp_kernel_fin_kernel<T>, blocks, GPK_THREADS, 0, st, f);
 }
 
 template <typename T, template <typename> class FAM>
 static int gp_bwd_launch(const GpkCallPlan& cp, const void* x, const void* z, const void* ls, int n_ls, const void* variance,
                          const void* alpha, const void* G, int64_t N, int64_t M, void* gx, void* gz, void* g_ls, void* g_var,
                          void* g_alpha, void* workspace, hipStream_t st) {
-  double* ws = (double*)workspace;
   const bool want_ls = g_ls != nullptr, any_scalar = g_ls || g_var || g_alpha;
-  if (cp.run_x) {
-    int rc = gp_bwd_side<T, FAM>(cp.x, (const T*)x, (const T*)(z ? z : x), (const T*)G, M, 1, z ? 0 : 1, (const T*)ls, n_ls,
-                                 (const T*)variance, (const T*)alpha, want_ls, any_scalar, ws, (T*)gx, (T*)g_ls,
-                                 (T*)g_var, (T*)g_alpha, st);
-    if (rc != PA_OK) return rc;
-  }
-  if (cp.run_z) {
-    const bool scalars = any_scalar && !cp.run_x;
-    int rc = gp_bwd_side<T, FAM>(cp.z, (const T*)z, (const T*)x, (const T*)G, 1, M, 0, (const T*)ls, n_ls,
-                                 (const T*)variance, (const T*)alpha, want_ls, scalars, ws + cp.z_offset_doubles, (T*)gz,
-                                 (T*)g_ls, (T*)g_var, (T*)g_alpha, st);
-    if (rc != PA_OK) return rc;
-  }
-  return PA_OK;
+  return gp_bwd_two_sided<T>(cp, x, z, M, gx, gz, any_scalar, workspace,
+                             [&](const GpkLaunchPlan& pl, const T* xr, const T* xc, int64_t g_sr, int64_t g_sc, bool sym,
+                                 bool scalars, double* ws, T* g_rows) {
+                               return gp_bwd_side<T, FAM>(pl, xr, xc, (const T*)G, g_sr, g_sc, sym ? 1 : 0, (const T*)ls, n_ls,
+                                                          (const T*)variance, (const T*)alpha, want_ls, scalars, ws, g_rows,
+                                                          (T*)g_ls, (T*)g_var, (T*)g_alpha, st);
+                             });
 }
-
-#define GPK_DISPATCH(CALL, ...)                                                       \
-  switch (family) {                                                                   \
-    case PA_GP_RBF: return CALL<T, GpRbf>(__VA_ARGS__);                               \
-    case PA_GP_RATIONAL_QUADRATIC: return CALL<T, GpRq>(__VA_ARGS__);                 \
-    case PA_GP_EXPONENTIAL: return CALL<T, GpExponential>(__VA_ARGS__);               \
-    case PA_GP_MATERN32: return CALL<T, GpMatern32>(__VA_ARGS__);                     \
-    default: return CALL<T, GpMatern52>(__VA_ARGS__);                                 \
-  }
 
 template <typename T>
 static int gp_fwd_family(int family, const void* x, const void* z, const void* ls, int n_ls, const void* variance,
                          const void* alpha, void* K, int64_t N, int64_t M, int D, hipStream_t st) {
-  GPK_DISPATCH(gp_fwd_launch, x, z, ls, n_ls, variance, alpha, K, N, M, D, st)
+  GP_FAMILY_DISPATCH(gp_fwd_launch, x, z, ls, n_ls, variance, alpha, K, N, M, D, st)
 }
 template <typename T>
 static int gp_bwd_family(int family, const GpkCallPlan& cp, const void* x, const void* z, const void* ls, int n_ls,
                          const void* variance, const void* alpha, const void* G, int64_t N, int64_t M, void* gx, void* gz,
                          void* g_ls, void* g_var, void* g_alpha, void* workspace, hipStream_t st) {
-  GPK_DISPATCH(gp_bwd_launch, cp, x, z, ls, n_ls, variance, alpha, G, N, M, gx, gz, g_ls, g_var, g_alpha, workspace, st)
+  GP_FAMILY_DISPATCH(gp_bwd_launch, cp, x, z, ls, n_ls, variance, alpha, G, N, M, gx, gz, g_ls, g_var, g_alpha, workspace, st)
 }
 
 static int gp_check(const char* who, int dtype, int family, const void* x, const void* ls, int n_ls, const void* variance,
@@ -391,7 +361,9 @@ int pa_gp_kernel_fwd(int dtype, int family, const void* x, const void* z, const 
 size_t pa_gp_kernel_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int want_gx, int want_gz,
                                   int forced_splits) {
   if (!pa::gpk_shape_ok(0, N, M, D, 1) || N == 0 || M == 0) return 0;
-  return pa::gpk_call_plan(N, M, (int)D, z_null != 0, want_gx != 0, want_gz != 0, pa::cu_count(), forced_splits).bytes;
+  return pa::gpk_call_plan(N, M, (int)D, pa::gpk_record_doubles((int)D), z_null != 0, want_gx != 0, want_gz != 0,
+                           pa::cu_count(), forced_splits)
+      .bytes;
 }
 
 int pa_gp_kernel_bwd(int dtype, int family, const void* x, const void* z, const void* lengthscale, int n_ls,
@@ -400,17 +372,15 @@ int pa_gp_kernel_bwd(int dtype, int family, const void* x, const void* z, const 
                      size_t workspace_bytes, pa_stream_t stream) {
   int rc = pa::gp_check("pa_gp_kernel_bwd", dtype, family, x, lengthscale, n_ls, variance, alpha, z, N, M, D);
   if (rc != PA_OK) return rc;
-  PA_REQUIRE(gz == nullptr || z != nullptr, "pa_gp_kernel_bwd: gz without a z (with z = x, gx takes both roles)");
   PA_REQUIRE(g_alpha == nullptr || family == PA_GP_RATIONAL_QUADRATIC, "pa_gp_kernel_bwd: g_alpha for family %d", family);
-  PA_REQUIRE(forced_splits >= 0, "pa_gp_kernel_bwd: forced_splits=%d", forced_splits);
-  if (!(gx || gz || g_lengthscale || g_variance || g_alpha)) return PA_OK;
-  PA_REQUIRE(N > 0 && M > 0, "pa_gp_kernel_bwd: an empty matrix has zero gradients; the caller fills them");
-  PA_REQUIRE(G != nullptr, "pa_gp_kernel_bwd: null G");
-  const pa::GpkCallPlan cp =
-      pa::gpk_call_plan(N, M, (int)D, z == nullptr, gx != nullptr, gz != nullptr, pa::cu_count(), forced_splits);
-  // the records of BOTH launches fit the workspace that was handed in (not merely the one sized by the caller's flags)
-  PA_REQUIRE(workspace != nullptr && cp.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_kernel_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, cp.bytes);
+  bool launch;
+  rc = pa::gp_bwd_preamble("pa_gp_kernel_bwd", z, gz, forced_splits, gx || gz || g_lengthscale || g_variance || g_alpha, N,
+                           M, G, &launch);
+  if (rc != PA_OK || !launch) return rc;
+  const pa::GpkCallPlan cp = pa::gpk_call_plan(N, M, (int)D, pa::gpk_record_doubles((int)D), z == nullptr, gx != nullptr,
+                                               gz != nullptr, pa::cu_count(), forced_splits);
+  rc = pa::gp_workspace_check("pa_gp_kernel_bwd", workspace, workspace_bytes, cp.bytes);
+  if (rc != PA_OK) return rc;
   PA_REQUIRE((!cp.run_x || (cp.x.row_doubles + cp.x.scalar_doubles) * sizeof(double) == cp.x.bytes) &&
                  (!cp.run_z || cp.z_offset_doubles * sizeof(double) + cp.z.bytes == cp.bytes),
              "pa_gp_kernel_bwd: inconsistent plan");

@@ -1,6 +1,8 @@
 // gp_kernel_plan.h -- host-side launch arithmetic of the stationary covariance kernels (gp_kernel.hip): tiles, column
-// splits, record counts, LDS and workspace bytes.  Plain C++ with no HIP in it, so that the same code is compiled into
-// a stand-alone host program and run under the address / undefined-behaviour sanitizers
+// splits, record counts, LDS and workspace bytes.  The launch and call plans serve every kernel on the 64 x 64 tile
+// (gp_periodic.hip, gp_compose.hip; gp_dot.hip takes the launch plan): they take the size of a workgroup's scalar
+// record, the one thing in which those kernels' workspaces differ.  Plain C++ with no HIP in it, so that the same code
+// is compiled into a stand-alone host program and run under the address / undefined-behaviour sanitizers
 // (tools/probes/gp_kernel_plan_check.cpp).
 #pragma once
 #include <stddef.h>
@@ -17,6 +19,7 @@ namespace pa {
 
 constexpr int GPK_TILE = 64;          // rows and columns of a workgroup's tile
 constexpr int GPK_THREADS = 256;      // 16 x 16 lanes, a 4 x 4 register tile of outputs each
+constexpr int GPK_WAVES = GPK_THREADS / 64;
 constexpr int GPK_MAX_D = 64;
 constexpr int GPK_FAMILIES = 5;       // PA_GP_RBF .. PA_GP_MATERN52
 constexpr int GPK_SCALARS = 3;        // per-workgroup scalar partials: variance, scale_mixture, scalar lengthscale
@@ -38,20 +41,24 @@ GPK_HD inline size_t gpk_lds_head_bytes(int D, size_t elem) { return (gpk_tile_e
 inline size_t gpk_fwd_lds_bytes(int D, size_t elem) { return gpk_lds_head_bytes(D, elem) + (size_t)D * sizeof(double); }
 // backward: the same, then the float64 row accumulators [TILE, D] and the per-wave lengthscale sums [4, D]
 inline size_t gpk_bwd_lds_bytes(int D, size_t elem) {
-  return gpk_lds_head_bytes(D, elem) + ((size_t)D + (size_t)GPK_TILE * D + (size_t)(GPK_THREADS / 64) * D) * sizeof(double);
+  return gpk_lds_head_bytes(D, elem) + ((size_t)D + (size_t)GPK_TILE * D + (size_t)GPK_WAVES * D) * sizeof(double);
 }
+
+// a workgroup's scalar record of gp_kernel.hip: {variance, scale_mixture, scalar lengthscale, lengthscale_k [D]}
+GPK_HD inline int gpk_record_doubles(int D) { return GPK_SCALARS + D; }
 
 // One backward launch: ``rows`` points get a gradient, ``cols`` points are walked.  Workgroup (row block, split) takes
 // column tiles [split * tiles_per_split, (split + 1) * tiles_per_split) and leaves one row record [TILE rows, D] in
-// slot ``split`` and one scalar record.
+// slot ``split`` and one scalar record of ``record`` float64 words.
 struct GpkLaunchPlan {
   int64_t rows, cols, row_blocks, col_tiles, tiles_per_split, workgroups;
   int splits, D;
   bool row_records;
-  size_t row_doubles, scalar_doubles, bytes;      // float64 words: [splits, rows, D] then [workgroups, SCALARS + D]
+  size_t row_doubles, scalar_doubles, bytes;      // float64 words: [splits, rows, D] then [workgroups, record]
 };
 
-inline GpkLaunchPlan gpk_launch_plan(int64_t rows, int64_t cols, int D, bool row_records, int cus, int forced_splits) {
+inline GpkLaunchPlan gpk_launch_plan(int64_t rows, int64_t cols, int D, int record, bool row_records, int cus,
+                                     int forced_splits) {
   GpkLaunchPlan pl;
   pl.rows = rows, pl.cols = cols, pl.D = D, pl.row_records = row_records;
   pl.row_blocks = gpk_tiles(rows);
@@ -68,12 +75,12 @@ inline GpkLaunchPlan gpk_launch_plan(int64_t rows, int64_t cols, int D, bool row
   pl.splits = (int)splits;
   pl.workgroups = pl.row_blocks * pl.splits;
   pl.row_doubles = row_records ? (size_t)pl.splits * (size_t)rows * (size_t)D : 0;
-  pl.scalar_doubles = (size_t)pl.workgroups * (size_t)(GPK_SCALARS + D);
+  pl.scalar_doubles = (size_t)pl.workgroups * (size_t)record;
   pl.bytes = (pl.row_doubles + pl.scalar_doubles) * sizeof(double);
   return pl;
 }
 
-// One call of pa_gp_kernel_bwd: the launch that gives x its gradient (and the reduced gradients), and, with a z of
+// One call of a tiled backward (pa_gp_kernel_bwd, pa_gp_periodic_bwd, pa_gp_compose_bwd): the launch that gives x its gradient (and the reduced gradients), and, with a z of
 // its own that wants a gradient, a second launch of the same kernel with the roles exchanged.  The reduced gradients
 // come from the first launch that runs.
 struct GpkCallPlan {
@@ -82,13 +89,13 @@ struct GpkCallPlan {
   size_t z_offset_doubles, bytes;
 };
 
-inline GpkCallPlan gpk_call_plan(int64_t N, int64_t M, int D, bool z_null, bool want_gx, bool want_gz, int cus,
-                                 int forced_splits) {
+inline GpkCallPlan gpk_call_plan(int64_t N, int64_t M, int D, int record, bool z_null, bool want_gx, bool want_gz,
+                                 int cus, int forced_splits) {
   GpkCallPlan cp;
   cp.run_z = want_gz && !z_null;
   cp.run_x = want_gx || !cp.run_z;
-  cp.x = gpk_launch_plan(N, z_null ? N : M, D, want_gx, cus, forced_splits);
-  cp.z = gpk_launch_plan(M, N, D, true, cus, forced_splits);
+  cp.x = gpk_launch_plan(N, z_null ? N : M, D, record, want_gx, cus, forced_splits);
+  cp.z = gpk_launch_plan(M, N, D, record, true, cus, forced_splits);
   if (!cp.run_x) cp.x.bytes = 0, cp.x.row_doubles = 0, cp.x.scalar_doubles = 0;
   if (!cp.run_z) cp.z.bytes = 0, cp.z.row_doubles = 0, cp.z.scalar_doubles = 0;
   cp.z_offset_doubles = cp.x.bytes / sizeof(double);

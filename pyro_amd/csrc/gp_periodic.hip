@@ -28,7 +28,8 @@
 // the failure the README documents for the Euclidean expansion of the stationary kernel.  So this kernel is VALU work.
 //
 // Tiles, splits, records: gp_kernel.hip's (64 x 64 tiles, 256 threads, 4 x 4 per lane, odd LDS row stride, column
-// splits that fill the device; gp_kernel_plan.h), with gp_periodic_plan.h for what differs.
+// splits that fill the device; gp_kernel_plan.h), with gp_periodic_plan.h for what differs.  The frame itself is
+// gp_tile.h's, the launch and the two-sided backward driver gp_host.h's, gp_exp_of gp_families.h's.
 //
 // Backward.  Nothing of the forward is kept: K is recomputed from the inputs (a model adds noise to its diagonal in
 // place).  With W = G K, a tile first forms the exponent (gpp_sinpi_reduced per pair and feature), then W, then walks the
@@ -47,8 +48,10 @@
 //
 // gfx950 cross-compile (hipcc -O3, -Rpass-analysis=kernel-resource-usage): no instantiation uses scratch; LDS is
 // dynamic; the register table is in the README entry "Gaussian processes".
-#include "gp_periodic_plan.h"
+#include "gp_families.h"
+#include "gp_host.h"
 #include "gp_periodic_dev.h"
+#include "gp_periodic_plan.h"
 
 namespace pa {
 
@@ -149,7 +152,7 @@ struct GppBwdArgs {
 template <typename T, bool SYM>
 __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_bwd_kernel(const GppBwdArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gp_lds[];
-  __shared__ double red[GPP_WAVES];
+  __shared__ double red[GPK_WAVES];
   const int D = a.D, stride = gpk_lds_stride(D);
   T* xs = reinterpret_cast<T*>(gp_lds);
   T* zs = xs + GPK_TILE * stride;
@@ -157,14 +160,14 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_bwd_kernel(const GppB
   double* inv_l2 = inv_p + D;                                                                  // [D]
   double* acc = inv_l2 + D;                                                                    // [64, D]
   double* ls_acc = acc + GPK_TILE * D;                                                         // [4, D]
-  double* p_acc = ls_acc + GPP_WAVES * D;                                                      // [4, D]
+  double* p_acc = ls_acc + GPK_WAVES * D;                                                      // [4, D]
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, lane = tid & 63, wave = tid >> 6;
   const int64_t rb = (int64_t)blockIdx.x / a.splits;
   const int split = (int)((int64_t)blockIdx.x - rb * a.splits);
   const int64_t i0 = rb * GPK_TILE;
   gp_stage(a.xr, i0, a.R, D, stride, xs);
   gpp_stage_parameters(a.ls, a.n_ls, a.period, a.n_p, D, inv_p, inv_l2);
-  for (int e = tid; e < (GPK_TILE + 2 * GPP_WAVES) * D; e += GPK_THREADS) acc[e] = 0.0;
+  for (int e = tid; e < (GPK_TILE + 2 * GPK_WAVES) * D; e += GPK_THREADS) acc[e] = 0.0;
   const bool ard = a.want_ls && a.n_ls != 1, per_feature = a.want_rows || ard || a.want_period;
   double s_var = 0.0, s_ls = 0.0;
   int64_t ct_end = (int64_t)(split + 1) * a.tiles_per_split;
@@ -220,35 +223,22 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_bwd_kernel(const GppB
       }
       if (a.want_rows) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const T total = gp_row16_sum(p[r]);
-          if (tx == 0) acc[(4 * ty + r) * D + k] += (double)total;
-        }
+        for (int r = 0; r < 4; ++r) gp_row_add(p[r], acc, (4 * ty + r) * D + k, tx);
       }
-      if (ard) {
-        const T total = wave_sum(ql);
-        if (lane == 0) ls_acc[wave * D + k] += (double)total;
-      }
-      if (a.want_period) {
-        const T total = wave_sum(qp);
-        if (lane == 0) p_acc[wave * D + k] += (double)total;
-      }
+      if (ard) gp_wave_add(ql, ls_acc, wave * D + k, lane);
+      if (a.want_period) gp_wave_add(qp, p_acc, wave * D + k, lane);
     }
   }
   __syncthreads();
-  if (a.want_rows) {
-    const int64_t rows_here = a.R - i0 < GPK_TILE ? a.R - i0 : GPK_TILE;
-    double* rec = a.row_rec + ((int64_t)split * a.R + i0) * D;
-    for (int64_t e = tid; e < rows_here * D; e += GPK_THREADS) rec[e] = acc[e];
-  }
+  if (a.want_rows) gp_copy_row_record(acc, a.row_rec, split, a.R, i0, D);
   if (a.want_scalars) {
     double* sc = a.sc_rec + (int64_t)blockIdx.x * gpp_record_doubles(D);
-    const double v0 = block_sum_f64_waves(s_var, red, GPP_WAVES);
-    const double v1 = block_sum_f64_waves(s_ls, red, GPP_WAVES);
+    const double v0 = block_sum_f64_waves(s_var, red, GPK_WAVES);
+    const double v1 = block_sum_f64_waves(s_ls, red, GPK_WAVES);
     if (tid == 0) sc[0] = v0, sc[1] = v1;
     for (int k = tid; k < D; k += GPK_THREADS) {
-      sc[GPP_SCALARS + k] = (ls_acc[k] + ls_acc[D + k]) + (ls_acc[2 * D + k] + ls_acc[3 * D + k]);
-      sc[GPP_SCALARS + D + k] = (p_acc[k] + p_acc[D + k]) + (p_acc[2 * D + k] + p_acc[3 * D + k]);
+      sc[GPP_SCALARS + k] = gp_fold_waves(ls_acc, k, D);
+      sc[GPP_SCALARS + D + k] = gp_fold_waves(p_acc, k, D);
     }
   }
 }
@@ -267,7 +257,7 @@ struct GppFinArgs {
 
 template <typename T>
 __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_fin_kernel(const GppFinArgs<T> a) {
-  __shared__ double red[GPP_WAVES];
+  __shared__ double red[GPK_WAVES];
   const double var = (double)a.variance[0];
   const auto l_of = [&](int k) { return (double)a.ls[a.n_ls == 1 ? 0 : k]; };
   const auto p_of = [&](int k) { return (double)a.period[a.n_p == 1 ? 0 : k]; };
@@ -275,8 +265,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_fin_kernel(const GppF
     const int64_t e = (int64_t)blockIdx.x * GPK_THREADS + threadIdx.x, total = a.R * a.D;
     if (e >= total) return;
     const int k = (int)(e % a.D);
-    double s = 0.0;
-    for (int sp = 0; sp < a.splits; ++sp) s += a.row_rec[(int64_t)sp * total + e];
+    const double s = gp_sum_splits(a.row_rec, a.splits, total, e);
     a.g_rows[e] = (T)(-2.0 * 3.14159265358979323846 * var / (p_of(k) * l_of(k) * l_of(k)) * s);
     return;
   }
@@ -304,7 +293,7 @@ __global__ __launch_bounds__(GPK_THREADS) void gp_periodic_fin_kernel(const GppF
     if (out == nullptr) return;
     for (int64_t w = threadIdx.x; w < a.workgroups; w += GPK_THREADS) s += a.sc_rec[w * rec];
   }
-  s = block_sum_f64_waves(s, red, GPP_WAVES);
+  s = block_sum_f64_waves(s, red, GPK_WAVES);
   if (threadIdx.x == 0) *out = (T)s;
 }
 
@@ -314,12 +303,9 @@ static int gpp_fwd_launch(const void* x, const void* z, const void* ls, int n_ls
                           const void* variance, void* K, int64_t N, int64_t M, int D, hipStream_t st) {
   const int64_t col_tiles = gpk_tiles(M), tiles = gpk_tiles(N) * col_tiles;
   PA_REQUIRE(tiles <= GPK_MAX_WORKGROUPS, "pa_gp_periodic_fwd: %lld tiles over the grid limit", (long long)tiles);
-  const size_t lds = gpp_fwd_lds_bytes(D, sizeof(T));
-  auto k = gp_periodic_fwd_kernel<T>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(GPK_THREADS), lds, st, (const T*)x, (const T*)(z ? z : x), (const T*)ls,
-                     n_ls, (const T*)period, n_p, (const T*)variance, (T*)K, N, M, D, col_tiles);
-  return check_launch("gp_periodic_fwd_kernel");
+  return gp_launch("gp_periodic_fwd_kernel", gp_periodic_fwd_kernel<T>, tiles, GPK_THREADS, gpp_fwd_lds_bytes(D, sizeof(T)), st,
+                   (const T*)x, (const T*)(z ? z : x), (const T*)ls, n_ls, (const T*)period, n_p, (const T*)variance, (T*)K,
+                   N, M, D, col_tiles);
 }
 
 template <typename T>
@@ -341,11 +327,8 @@ static int gpp_bwd_side(const GpkLaunchPlan& pl, const T* xr, const T* xc, const
   a.want_ls = scalars && pr.g_ls ? 1 : 0, a.want_period = scalars && pr.g_period ? 1 : 0;
   a.R = pl.rows, a.C = pl.cols, a.tiles_per_split = pl.tiles_per_split, a.col_tiles = pl.col_tiles;
   a.row_rec = ws, a.sc_rec = ws + pl.row_doubles;
-  const size_t lds = gpp_bwd_lds_bytes(pl.D, sizeof(T));
-  auto k = sym ? gp_periodic_bwd_kernel<T, true> : gp_periodic_bwd_kernel<T, false>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPK_THREADS), lds, st, a);
-  int rc = check_launch("gp_periodic_bwd_kernel");
+  int rc = gp_launch("gp_periodic_bwd_kernel", sym ? gp_periodic_bwd_kernel<T, true> : gp_periodic_bwd_kernel<T, false>,
+                     pl.workgroups, GPK_THREADS, gpp_bwd_lds_bytes(pl.D, sizeof(T)), st, a);
   if (rc != PA_OK) return rc;
   GppFinArgs<T> f;
   f.row_rec = a.row_rec, f.sc_rec = a.sc_rec, f.ls = pr.ls, f.period = pr.period, f.variance = pr.variance;
@@ -355,24 +338,17 @@ static int gpp_bwd_side(const GpkLaunchPlan& pl, const T* xr, const T* xc, const
   const int64_t blocks = f.row_fin_blocks + (scalars ? pr.n_ls + pr.n_p + 1 : 0);
   if (blocks == 0) return PA_OK;
   PA_REQUIRE(blocks <= GPK_MAX_WORKGROUPS, "pa_gp_periodic_bwd: finalize grid of %lld blocks", (long long)blocks);
-  hipLaunchKernelGGL(gp_periodic_fin_kernel<T>, dim3((unsigned)blocks), dim3(GPK_THREADS), 0, st, f);
-  return check_launch("gp_periodic_fin_kernel");
+  return gp_launch("gp_periodic_fin_kernel", gp_periodic_fin_kernel<T>, blocks, GPK_THREADS, 0, st, f);
 }
 
 template <typename T>
 static int gpp_bwd_launch(const GpkCallPlan& cp, const void* x, const void* z, const GppParams<T>& pr, const void* G,
                           int64_t M, void* gx, void* gz, void* workspace, hipStream_t st) {
-  double* ws = (double*)workspace;
-  const bool any_scalar = pr.g_ls || pr.g_period || pr.g_var;
-  if (cp.run_x) {
-    int rc = gpp_bwd_side<T>(cp.x, (const T*)x, (const T*)(z ? z : x), (const T*)G, M, 1, z == nullptr, pr, any_scalar, ws,
-                             (T*)gx, st);
-    if (rc != PA_OK) return rc;
-  }
-  if (cp.run_z)
-    return gpp_bwd_side<T>(cp.z, (const T*)z, (const T*)x, (const T*)G, 1, M, false, pr, any_scalar && !cp.run_x,
-                           ws + cp.z_offset_doubles, (T*)gz, st);
-  return PA_OK;
+  return gp_bwd_two_sided<T>(cp, x, z, M, gx, gz, pr.g_ls || pr.g_period || pr.g_var, workspace,
+                             [&](const GpkLaunchPlan& pl, const T* xr, const T* xc, int64_t g_sr, int64_t g_sc, bool sym,
+                                 bool scalars, double* ws, T* g_rows) {
+                               return gpp_bwd_side<T>(pl, xr, xc, (const T*)G, g_sr, g_sc, sym, pr, scalars, ws, g_rows, st);
+                             });
 }
 
 static int gpp_check(const char* who, int dtype, const void* x, const void* z, const void* ls, int n_ls, const void* period,
@@ -406,7 +382,9 @@ int pa_gp_periodic_fwd(int dtype, const void* x, const void* z, const void* leng
 size_t pa_gp_periodic_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int want_gx, int want_gz,
                                     int forced_splits) {
   if (!pa::gpp_shape_ok(N, M, D, 1, 1) || N == 0 || M == 0) return 0;
-  return pa::gpp_call_plan(N, M, (int)D, z_null != 0, want_gx != 0, want_gz != 0, pa::cu_count(), forced_splits).bytes;
+  return pa::gpk_call_plan(N, M, (int)D, pa::gpp_record_doubles((int)D), z_null != 0, want_gx != 0, want_gz != 0,
+                           pa::cu_count(), forced_splits)
+      .bytes;
 }
 
 int pa_gp_periodic_bwd(int dtype, const void* x, const void* z, const void* lengthscale, int n_ls, const void* period,
@@ -415,16 +393,14 @@ int pa_gp_periodic_bwd(int dtype, const void* x, const void* z, const void* leng
                        void* workspace, size_t workspace_bytes, pa_stream_t stream) {
   int rc = pa::gpp_check("pa_gp_periodic_bwd", dtype, x, z, lengthscale, n_ls, period, n_period, variance, N, M, D);
   if (rc != PA_OK) return rc;
-  PA_REQUIRE(gz == nullptr || z != nullptr, "pa_gp_periodic_bwd: gz without a z (with z = x, gx takes both roles)");
-  PA_REQUIRE(forced_splits >= 0, "pa_gp_periodic_bwd: forced_splits=%d", forced_splits);
-  if (!(gx || gz || g_lengthscale || g_period || g_variance)) return PA_OK;
-  PA_REQUIRE(N > 0 && M > 0, "pa_gp_periodic_bwd: an empty matrix has zero gradients; the caller fills them");
-  PA_REQUIRE(G != nullptr, "pa_gp_periodic_bwd: null G");
-  const pa::GpkCallPlan cp =
-      pa::gpp_call_plan(N, M, (int)D, z == nullptr, gx != nullptr, gz != nullptr, pa::cu_count(), forced_splits);
-  // the records of BOTH launches fit the workspace that was handed in (not merely the one sized by the caller's flags)
-  PA_REQUIRE(workspace != nullptr && cp.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_periodic_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, cp.bytes);
+  bool launch;
+  rc = pa::gp_bwd_preamble("pa_gp_periodic_bwd", z, gz, forced_splits, gx || gz || g_lengthscale || g_period || g_variance,
+                           N, M, G, &launch);
+  if (rc != PA_OK || !launch) return rc;
+  const pa::GpkCallPlan cp = pa::gpk_call_plan(N, M, (int)D, pa::gpp_record_doubles((int)D), z == nullptr, gx != nullptr,
+                                               gz != nullptr, pa::cu_count(), forced_splits);
+  rc = pa::gp_workspace_check("pa_gp_periodic_bwd", workspace, workspace_bytes, cp.bytes);
+  if (rc != PA_OK) return rc;
   hipStream_t st = pa::as_stream(stream);
   if (dtype == PA_F32) {
     const pa::GppParams<float> pr = {(const float*)lengthscale, (const float*)period, (const float*)variance, n_ls,

@@ -8,7 +8,8 @@
 // LowRankMultivariateNormal (W^T D^-1 W, W^T r, W.pow(2).sum()), all of them [M, N] and all kept by autograd.
 //
 // r2 is gp_kernel.hip's: the difference first, (xu - x) * (1 / l), its square summed in float64 for both dtypes and
-// kept in float64 up to the exponential.  The family functions are copies of that file's (it stays untouched).
+// kept in float64 up to the exponential.  The family functions are gp_families.h's, the ones that file evaluates; the
+// wave's block, the staging and r2 are gp_sparse_dev.h's, shared with gp_cond.hip.
 //
 // Matrix cores.  One primitive, gps_mac: C [32, 32] += A [32, K] B [K, 32] for one wave, the result in the register
 // layout of v_mfma_f32_32x32x2_f32 (lane l holds column l % 32 and rows 8 (v / 4) + 4 (l / 32) + v % 4, v < 16).  In
@@ -31,99 +32,11 @@
 // recomputed for the lane's 16 entries, w = G f', and the float64 accumulators [128, D] in LDS have one writer per
 // entry.  gr is written directly by chunk 0 from the staged tile; gx leaves one partial per chunk (w goes through LDS
 // once, then one thread per (point, feature)).  The finalize kernel sums records and applies 2 variance / l_k.
-#include "common.h"
-#include "gp_sgpr_plan.h"
+#include "gp_families.h"
+#include "gp_host.h"
+#include "gp_sparse_dev.h"
 
 namespace pa {
-
-template <typename T>
-__device__ __forceinline__ T gps_exp(T v) {
-  if constexpr (sizeof(T) == 4) return expf(v);
-  else return exp(v);
-}
-template <typename T>
-__device__ __forceinline__ T gps_log1p(T v) {
-  if constexpr (sizeof(T) == 4) return log1pf(v);
-  else return log1p(v);
-}
-// exp(a) for an argument held in float64; in float32 exp(hi + lo) = exp(hi) (1 + lo) (gp_kernel.hip: gp_exp_of)
-template <typename T>
-__device__ __forceinline__ T gps_exp_of(double a) {
-  if constexpr (sizeof(T) == 8) {
-    return exp(a);
-  } else {
-    const float hi = (float)a, lo = (float)(a - (double)hi);
-    return expf(hi) * (1.0f + lo);
-  }
-}
-
-// eval(r2 in float64, alpha) -> f, df = df / d(r2), da = df / d(alpha)
-template <typename T>
-struct GpsRbf {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    f = gps_exp_of<T>(-0.5 * r2);
-    df = T(-0.5) * f;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpsRq {
-  __device__ __forceinline__ static void eval(double r2d, T alpha, T& f, T& df, T& da) {
-    const T u = (T)r2d / (T(2) * alpha), l1 = gps_log1p(u);
-    f = gps_exp(-alpha * l1);
-    df = T(-0.5) * f / (T(1) + u);
-    da = f * (u / (T(1) + u) - l1);
-  }
-};
-template <typename T>
-struct GpsExponential {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double r = sqrt(r2 + 1e-12);
-    f = gps_exp_of<T>(-r);
-    df = T(-0.5) * f / (T)r;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpsMatern32 {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double sr = 1.7320508075688772935 * sqrt(r2 + 1e-12);
-    const T e = gps_exp_of<T>(-sr);
-    f = (T(1) + (T)sr) * e;
-    df = T(-1.5) * e;
-    da = T(0);
-  }
-};
-template <typename T>
-struct GpsMatern52 {
-  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
-    const double r = sqrt(r2 + 1e-12), sr = 2.2360679774997896964 * r;
-    const T e = gps_exp_of<T>(-sr);
-    f = (T(1) + (T)sr + T(5.0 / 3.0) * (T)r2) * e;
-    df = e * (T(-5.0 / 6.0) - T(5.0 * 2.2360679774997896964 / 6.0) * (T)(r2 / r));
-    da = T(0);
-  }
-};
-
-// ---- the 32 x 32 block of one wave ----------------------------------------------------------------------------------
-typedef float gps_f32x16 __attribute__((ext_vector_type(16)));
-template <typename T>
-struct GpsAcc;
-template <>
-struct GpsAcc<float> {
-  gps_f32x16 c;
-};
-template <>
-struct GpsAcc<double> {
-  double c[16];
-};
-template <typename T>
-__device__ __forceinline__ void gps_clear(GpsAcc<T>& a) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) a.c[v] = T(0);
-}
-// the row of the block that register v of lane ``lane`` holds (its column is lane % 32)
-__device__ __forceinline__ int gps_row(int v, int lane) { return 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3); }
 
 // C += A B.  A(i, k) = A[i * a_si + k * a_sk], i < 32 (always readable); B(k, j) = B[k * b_sk + j * b_sj], read only
 // where b_ok (the lane's column j = lane % 32 exists), zero otherwise; k < K
@@ -148,28 +61,6 @@ __device__ __forceinline__ void gps_mac(GpsAcc<T>& acc, const T* A, int a_si, in
       for (int v = 0; v < 16; ++v) acc.c[v] = fma(A[gps_row(v, lane) * a_si + k * a_sk], bv, acc.c[v]);
     }
   }
-}
-
-// rows [first, first + rows) of p [n, D] into tile [rows, stride], zeros past the end
-template <typename T>
-__device__ __forceinline__ void gps_stage(const T* __restrict__ p, int64_t first, int64_t n, int rows, int D, int stride,
-                                          T* tile) {
-  for (int e = threadIdx.x; e < rows * D; e += GPS_THREADS) {
-    const int row = e / D, k = e - row * D;
-    const int64_t i = first + row;
-    tile[row * stride + k] = i < n ? p[i * D + k] : T(0);
-  }
-}
-
-// r2 of (u, x) in float64: the difference first, then 1 / l (gp_kernel.hip: gp_r2_tile)
-template <typename T>
-__device__ __forceinline__ double gps_r2(const T* u, const T* x, const double* inv_l, int D) {
-  double s = 0.0;
-  for (int k = 0; k < D; ++k) {
-    const double d = ((double)u[k] - (double)x[k]) * inv_l[k];
-    s = fma(d, d, s);
-  }
-  return s;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
@@ -513,11 +404,6 @@ __global__ __launch_bounds__(GPS_THREADS) void gp_sgpr_bwd_fin_kernel(const GpsF
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
-template <typename K>
-static void gps_allow_lds(K kernel, size_t lds) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 template <typename T, template <typename> class FAM>
 static int gps_fwd_launch(const GpsFwdPlan& pl, const void* x, const void* xu, const void* r, const void* ls, int n_ls,
                           const void* variance, const void* alpha, void* A, void* b, int64_t N, int64_t M, void* workspace,
@@ -528,10 +414,7 @@ static int gps_fwd_launch(const GpsFwdPlan& pl, const void* x, const void* xu, c
   a.rec_dim = pl.rec_dim, a.N = N, a.M = M, a.steps = pl.steps, a.steps_per_split = pl.steps_per_split;
   a.a_rec = (double*)workspace, a.b_rec = a.a_rec + pl.a_doubles;
   constexpr int TM = sizeof(T) == 4 ? 128 : 64;
-  auto k = gp_sgpr_fwd_kernel<T, FAM, TM>;
-  gps_allow_lds(k, pl.lds_bytes);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPS_THREADS), pl.lds_bytes, st, a);
-  int rc = check_launch("gp_sgpr_fwd_kernel");
+  int rc = gp_launch("gp_sgpr_fwd_kernel", gp_sgpr_fwd_kernel<T, FAM, TM>, pl.workgroups, GPS_THREADS, pl.lds_bytes, st, a);
   if (rc != PA_OK) return rc;
   const int a_blocks = (int)gps_div_up(M * M, GPS_THREADS), b_blocks = (int)gps_div_up(M * pl.Q, GPS_THREADS);
   hipLaunchKernelGGL(gp_sgpr_fwd_fin_kernel<T>, dim3((unsigned)(a_blocks + b_blocks)), dim3(GPS_THREADS), 0, st, a.a_rec,
@@ -561,10 +444,7 @@ static int gps_bwd_launch(const GpsBwdPlan& pl, const void* x, const void* xu, c
   a.want_gx = pl.want_gx ? 1 : 0, a.N = N, a.steps = pl.steps, a.steps_per_split = pl.steps_per_split;
   a.row_rec = ws + pl.s_doubles, a.sc_rec = a.row_rec + pl.row_doubles, a.gx_rec = a.sc_rec + pl.scalar_doubles;
   a.gr = (T*)o.gr;
-  auto k = gp_sgpr_bwd_kernel<T, FAM>;
-  gps_allow_lds(k, pl.lds_bytes);
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.workgroups), dim3(GPS_THREADS), pl.lds_bytes, st, a);
-  rc = check_launch("gp_sgpr_bwd_kernel");
+  rc = gp_launch("gp_sgpr_bwd_kernel", gp_sgpr_bwd_kernel<T, FAM>, pl.workgroups, GPS_THREADS, pl.lds_bytes, st, a);
   if (rc != PA_OK) return rc;
   GpsFinArgs<T> f;
   f.row_rec = a.row_rec, f.sc_rec = a.sc_rec, f.gx_rec = a.gx_rec, f.ls = a.ls, f.variance = a.variance, f.n_ls = n_ls;
@@ -579,26 +459,17 @@ static int gps_bwd_launch(const GpsBwdPlan& pl, const void* x, const void* xu, c
   return check_launch("gp_sgpr_bwd_fin_kernel");
 }
 
-#define GPS_DISPATCH(CALL, ...)                                                        \
-  switch (family) {                                                                    \
-    case PA_GP_RBF: return CALL<T, GpsRbf>(__VA_ARGS__);                               \
-    case PA_GP_RATIONAL_QUADRATIC: return CALL<T, GpsRq>(__VA_ARGS__);                 \
-    case PA_GP_EXPONENTIAL: return CALL<T, GpsExponential>(__VA_ARGS__);               \
-    case PA_GP_MATERN32: return CALL<T, GpsMatern32>(__VA_ARGS__);                     \
-    default: return CALL<T, GpsMatern52>(__VA_ARGS__);                                 \
-  }
-
 template <typename T>
 static int gps_fwd_family(int family, const GpsFwdPlan& pl, const void* x, const void* xu, const void* r, const void* ls,
                           int n_ls, const void* variance, const void* alpha, void* A, void* b, int64_t N, int64_t M,
                           void* workspace, hipStream_t st) {
-  GPS_DISPATCH(gps_fwd_launch, pl, x, xu, r, ls, n_ls, variance, alpha, A, b, N, M, workspace, st)
+  GP_FAMILY_DISPATCH(gps_fwd_launch, pl, x, xu, r, ls, n_ls, variance, alpha, A, b, N, M, workspace, st)
 }
 template <typename T>
 static int gps_bwd_family(int family, const GpsBwdPlan& pl, const void* x, const void* xu, const void* r, const void* ls,
                           int n_ls, const void* variance, const void* alpha, const void* gA, const void* gb, int64_t N,
                           int64_t M, const GpsBwdOut& o, void* workspace, hipStream_t st) {
-  GPS_DISPATCH(gps_bwd_launch, pl, x, xu, r, ls, n_ls, variance, alpha, gA, gb, N, M, o, workspace, st)
+  GP_FAMILY_DISPATCH(gps_bwd_launch, pl, x, xu, r, ls, n_ls, variance, alpha, gA, gb, N, M, o, workspace, st)
 }
 
 static int gps_check(const char* who, int dtype, int family, const void* x, const void* xu, const void* r, const void* ls,
@@ -640,8 +511,8 @@ int pa_gp_sgpr_fwd(int dtype, int family, const void* x, const void* xu, const v
   PA_REQUIRE(A != nullptr && b != nullptr, "pa_gp_sgpr_fwd: null output");
   const size_t elem = dtype == PA_F32 ? 4 : 8;
   const pa::GpsFwdPlan pl = pa::gps_fwd_plan(N, M, (int)D, (int)Q, elem, pa::cu_count(), forced_splits);
-  PA_REQUIRE(workspace != nullptr && pl.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_sgpr_fwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, pl.bytes);
+  rc = pa::gp_workspace_check("pa_gp_sgpr_fwd", workspace, workspace_bytes, pl.bytes);
+  if (rc != PA_OK) return rc;
   PA_REQUIRE(pl.workgroups <= pa::GPS_MAX_WORKGROUPS && (pl.a_doubles + pl.b_doubles) * sizeof(double) == pl.bytes,
              "pa_gp_sgpr_fwd: inconsistent plan");
   hipStream_t st = pa::as_stream(stream);
@@ -664,8 +535,8 @@ int pa_gp_sgpr_bwd(int dtype, int family, const void* x, const void* xu, const v
   const size_t elem = dtype == PA_F32 ? 4 : 8;
   const pa::GpsBwdPlan pl =
       pa::gps_bwd_plan(N, M, (int)D, (int)Q, elem, gx != nullptr, gxu != nullptr, pa::cu_count(), forced_splits);
-  PA_REQUIRE(workspace != nullptr && pl.bytes <= workspace_bytes && (uintptr_t)workspace % 8 == 0,
-             "pa_gp_sgpr_bwd: workspace of %zu bytes, the plan needs %zu (8-byte aligned)", workspace_bytes, pl.bytes);
+  rc = pa::gp_workspace_check("pa_gp_sgpr_bwd", workspace, workspace_bytes, pl.bytes);
+  if (rc != PA_OK) return rc;
   PA_REQUIRE(pl.workgroups <= pa::GPS_MAX_WORKGROUPS &&
                  (pl.s_doubles + pl.row_doubles + pl.scalar_doubles + pl.gx_doubles) * sizeof(double) == pl.bytes,
              "pa_gp_sgpr_bwd: inconsistent plan");

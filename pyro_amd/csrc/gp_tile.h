@@ -1,6 +1,12 @@
-// gp_tile.h -- what the tiled covariance kernels share (gp_kernel.hip, gp_periodic.hip): the 4-wide vector, the
-// exponential of a float64 argument, the staging of a 64-row tile, the load of a thread's 4 x 4 entries of the incoming
-// gradient and the sum over the 16 lanes of a row.  Geometry: gp_kernel_plan.h.
+// gp_tile.h -- the frame that the kernels on the 64 x 64 tile share (gp_kernel.hip, gp_periodic.hip, gp_compose.hip;
+// gp_dot.hip takes the row-record copy and the sum over the splits): the 4-wide vector, the staging of
+// a 64-row tile, the load of a thread's 4 x 4 entries of the incoming gradient, the adds into the one-writer float64
+// accumulators, the four-wave fold, the row-record copy and the finalize's sum over the splits.  (Two pieces of the
+// frame stay spelt out in the kernels, because as functions they changed the compiler's instruction schedule: the
+// vectorised-or-masked store of K in the three forward kernels, and the decode of blockIdx.x into row block and split
+// with the split's column-tile range in the four backward kernels.)  Each is the text that those kernels
+// spelt out before, so the float64 summation orders -- and with them the bit-reproducibility that the kernels' file
+// heads promise -- are in one place.  Geometry: gp_kernel_plan.h.
 #pragma once
 #include "common.h"
 #include "gp_kernel_plan.h"
@@ -11,18 +17,6 @@ template <typename T>
 struct alignas(4 * sizeof(T)) Vec4 {
   T v[4];
 };
-
-// exp(a) for an argument held in float64.  In float32 the argument is split into its rounded value and the remainder,
-// exp(hi + lo) = exp(hi) (1 + lo): rounding a = -r2 / 2 to float32 alone would cost |a| 2^-24 relative (4e-6 at r2 = 130).
-template <typename T>
-__device__ __forceinline__ T gp_exp_of(double a) {
-  if constexpr (sizeof(T) == 8) {
-    return exp(a);
-  } else {
-    const float hi = (float)a, lo = (float)(a - (double)hi);
-    return expf(hi) * (1.0f + lo);
-  }
-}
 
 // ---- staging: rows [first, first + 64) of p [n, D] into tile [64, stride], zeros past the end ----------------------
 template <typename T>
@@ -71,6 +65,46 @@ __device__ __forceinline__ void gp_load_g(const ARGS<T>& a, int64_t sr, int64_t 
 #pragma unroll
       for (int c = 0; c < 4; ++c) g[r][c] = (i + r < a.R && j + c < a.C) ? a.G[(i + r) * sr + (j + c) * sc] : T(0);
   }
+}
+
+// ---- the float64 accumulators in LDS, one writer per entry ------------------------------------------------------------
+// a thread's sum p over its 4 columns of one row and feature: the 16 lanes of the row add theirs on DPP and lane
+// tx = 0, the only writer of that row, adds the result to acc[entry] of the row accumulator
+template <typename T>
+__device__ __forceinline__ void gp_row_add(T p, double* acc, int entry, int tx) {
+  const T total = gp_row16_sum(p);
+  if (tx == 0) acc[entry] += (double)total;
+}
+// the same with the sum scaled first (gp_compose.hip: the scale differs from factor to factor)
+template <typename T>
+__device__ __forceinline__ void gp_row_add(T p, double scale, double* acc, int entry, int tx) {
+  const T total = gp_row16_sum(p);
+  if (tx == 0) acc[entry] += scale * (double)total;
+}
+// the wave's sum of q to acc[entry], an entry of the wave's own
+template <typename T>
+__device__ __forceinline__ void gp_wave_add(T q, double* acc, int entry, int lane) {
+  const T total = wave_sum(q);
+  if (lane == 0) acc[entry] += (double)total;
+}
+// entry k of the four waves' accumulators a [4, step], in the fixed order (a0 + a1) + (a2 + a3)
+__device__ __forceinline__ double gp_fold_waves(const double* a, int k, int step) {
+  return (a[k] + a[step + k]) + (a[2 * step + k] + a[3 * step + k]);
+}
+
+// ---- records ------------------------------------------------------------------------------------------------------------
+// the row block's accumulator [64, width] to slot ``split`` of the row records [splits, R, width]
+__device__ __forceinline__ void gp_copy_row_record(const double* acc, double* row_rec, int split, int64_t R, int64_t i0,
+                                                   int width) {
+  const int64_t rows_here = R - i0 < GPK_TILE ? R - i0 : GPK_TILE;
+  double* rec = row_rec + ((int64_t)split * R + i0) * width;
+  for (int64_t e = threadIdx.x; e < rows_here * width; e += GPK_THREADS) rec[e] = acc[e];
+}
+// the finalize's sum over the splits for entry e of the ``total`` entries of a row record, in split order
+__device__ __forceinline__ double gp_sum_splits(const double* row_rec, int splits, int64_t total, int64_t e) {
+  double s = 0.0;
+  for (int sp = 0; sp < splits; ++sp) s += row_rec[(int64_t)sp * total + e];
+  return s;
 }
 
 }  // namespace pa

@@ -1132,24 +1132,56 @@ GP_FAMILIES = {"rbf": 0, "rational_quadratic": 1, "exponential": 2, "matern32": 
 GP_KERNEL_MAX_D = 64                      # (csrc/gp_kernel_plan.h GPK_MAX_D)
 
 
+# What gp_kernel_*, gp_periodic_*, gp_dot_* and gp_compose_* share.  ``name`` is the caller's, for the messages.
+def _gp_points(name, x, z, width="D"):
+    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), \
+        "%s: x [N, %s], z [M, %s]" % (name, width, width)
+
+
+def _gp_one_dtype(name, x, tensors):
+    for t in tensors:
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError("pyro_amd: %s: one dtype throughout, got %s and %s" % (name, x.dtype, t.dtype))
+
+
+def _gp_contiguous(*tensors):
+    return tuple(None if t is None else t.contiguous() for t in tensors)
+
+
+def _gp_new_K(x, z):
+    """(N, M, K [N, M] uninitialised); an empty K makes no launch."""
+    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
+    return N, M, x.new_empty((N, M))
+
+
+def _gp_incoming(name, x, z, G):
+    """(N, M, G contiguous, empty, make) of a backward: ``make`` allocates a wanted gradient."""
+    _require_gpu(G)
+    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
+    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "%s: G [N, M] of x's dtype" % name
+    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
+    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
+    return N, M, G.contiguous(), empty, make
+
+
+def _gp_workspace(nbytes, x):
+    return torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+
+
 def _gp_kernel_args(x, z, lengthscale, variance, alpha, family):
     family = GP_FAMILIES.get(family, family)
     assert family in (0, 1, 2, 3, 4), "gp_kernel: family is 0..4 or one of %s" % sorted(GP_FAMILIES)
     _require_gpu(x, z, lengthscale, variance, alpha)
-    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_kernel: x [N, D], z [M, D]"
+    _gp_points("gp_kernel", x, z)
     D = x.shape[1]
     if not 1 <= D <= GP_KERNEL_MAX_D:
         raise Unsupported("pyro_amd: gp_kernel: D=%d outside [1, %d]" % (D, GP_KERNEL_MAX_D))
-    for t in (z, lengthscale, variance, alpha):
-        if t is not None and t.dtype != x.dtype:
-            raise ValueError("pyro_amd: gp_kernel: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    _gp_one_dtype("gp_kernel", x, (z, lengthscale, variance, alpha))
     if lengthscale.numel() not in (1, D) or variance.numel() != 1 or (alpha is not None and alpha.numel() != 1):
         raise ValueError("pyro_amd: gp_kernel: lengthscale has 1 or D elements, variance and scale_mixture 1")
     if (family == 1) != (alpha is not None):
         raise ValueError("pyro_amd: gp_kernel: scale_mixture goes with the RationalQuadratic family, and only with it")
-    x = x.contiguous()
-    z = None if z is None else z.contiguous()
-    return family, x, z, lengthscale.contiguous(), variance.contiguous(), None if alpha is None else alpha.contiguous()
+    return (family,) + _gp_contiguous(x, z, lengthscale, variance, alpha)
 
 
 def gp_kernel_fwd(x, z, lengthscale, variance, alpha=None, family="rbf"):
@@ -1158,13 +1190,11 @@ def gp_kernel_fwd(x, z, lengthscale, variance, alpha=None, family="rbf"):
     "rational_quadratic") alpha of one: device tensors of x's dtype (f32 / f64), read by the kernel.  D over
     GP_KERNEL_MAX_D raises Unsupported; an empty result makes no launch."""
     family, x, z, lengthscale, variance, alpha = _gp_kernel_args(x, z, lengthscale, variance, alpha, family)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    K = x.new_empty((N, M))
+    N, M, K = _gp_new_K(x, z)
     if N == 0 or M == 0:
         return K
     check(_lib.load().pa_gp_kernel_fwd(_dtype(x), family, _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(),
-                                       _ptr(variance), _ptr(alpha), _ptr(K), N, M, D, _stream()))
+                                       _ptr(variance), _ptr(alpha), _ptr(K), N, M, x.shape[1], _stream()))
     return K
 
 
@@ -1176,16 +1206,11 @@ def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(Tru
     over G per side that wants a gradient, then a fixed-order float64 finalize (pa_gp_kernel_bwd): bit-reproducible.
     ``forced_splits`` > 0 fixes the number of column splits (tests)."""
     family, x, z, lengthscale, variance, alpha = _gp_kernel_args(x, z, lengthscale, variance, alpha, family)
-    _require_gpu(G)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_kernel_bwd: G [N, M] of x's dtype"
-    G = G.contiguous()
+    N, M, G, empty, make = _gp_incoming("gp_kernel_bwd", x, z, G)
+    D = x.shape[1]
     want_gx, want_gz, want_ls, want_var, want_alpha = (bool(w) for w in want)
     want_gz = want_gz and z is not None
     want_alpha = want_alpha and alpha is not None
-    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
-    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
     gx = make(x) if want_gx else None
     gz = make(z) if want_gz else None
     g_ls = make(lengthscale) if want_ls else None
@@ -1194,8 +1219,8 @@ def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(Tru
     if empty or not (want_gx or want_gz or want_ls or want_var or want_alpha):
         return gx, gz, g_ls, g_var, g_alpha
     lib = _lib.load()
-    nbytes = lib.pa_gp_kernel_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _gp_workspace(lib.pa_gp_kernel_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz),
+                                                      int(forced_splits)), x)
     check(lib.pa_gp_kernel_bwd(_dtype(x), family, _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(variance),
                                _ptr(alpha), _ptr(G), N, M, D, _ptr(gx), _ptr(gz), _ptr(g_ls), _ptr(g_var), _ptr(g_alpha),
                                int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
@@ -1204,17 +1229,14 @@ def gp_kernel_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", want=(Tru
 
 def _gp_periodic_args(x, z, lengthscale, period, variance):
     _require_gpu(x, z, lengthscale, period, variance)
-    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_periodic: x [N, D], z [M, D]"
+    _gp_points("gp_periodic", x, z)
     D = x.shape[1]
     if not 1 <= D <= GP_KERNEL_MAX_D:
         raise Unsupported("pyro_amd: gp_periodic: D=%d outside [1, %d]" % (D, GP_KERNEL_MAX_D))
-    for t in (z, lengthscale, period, variance):
-        if t is not None and t.dtype != x.dtype:
-            raise ValueError("pyro_amd: gp_periodic: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    _gp_one_dtype("gp_periodic", x, (z, lengthscale, period, variance))
     if lengthscale.numel() not in (1, D) or period.numel() not in (1, D) or variance.numel() != 1:
         raise ValueError("pyro_amd: gp_periodic: lengthscale and period have 1 or D elements each, variance 1")
-    return (x.contiguous(), None if z is None else z.contiguous(), lengthscale.contiguous(), period.contiguous(),
-            variance.contiguous())
+    return _gp_contiguous(x, z, lengthscale, period, variance)
 
 
 def gp_periodic_fwd(x, z, lengthscale, period, variance):
@@ -1223,13 +1245,11 @@ def gp_periodic_fwd(x, z, lengthscale, period, variance):
     D elements each, variance of one: device tensors of x's dtype (f32 / f64), read by the kernel.  D over
     GP_KERNEL_MAX_D raises Unsupported; an empty result makes no launch."""
     x, z, lengthscale, period, variance = _gp_periodic_args(x, z, lengthscale, period, variance)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    K = x.new_empty((N, M))
+    N, M, K = _gp_new_K(x, z)
     if N == 0 or M == 0:
         return K
     check(_lib.load().pa_gp_periodic_fwd(_dtype(x), _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(period),
-                                         period.numel(), _ptr(variance), _ptr(K), N, M, D, _stream()))
+                                         period.numel(), _ptr(variance), _ptr(K), N, M, x.shape[1], _stream()))
     return K
 
 
@@ -1239,15 +1259,10 @@ def gp_periodic_bwd(x, z, lengthscale, period, variance, G, want=(True, True, Tr
     is not an argument -- in one pass over G per side that wants a gradient, then a fixed-order float64 finalize
     (pa_gp_periodic_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the number of column splits (tests)."""
     x, z, lengthscale, period, variance = _gp_periodic_args(x, z, lengthscale, period, variance)
-    _require_gpu(G)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_periodic_bwd: G [N, M] of x's dtype"
-    G = G.contiguous()
+    N, M, G, empty, make = _gp_incoming("gp_periodic_bwd", x, z, G)
+    D = x.shape[1]
     want_gx, want_gz, want_ls, want_period, want_var = (bool(w) for w in want)
     want_gz = want_gz and z is not None
-    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
-    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
     gx = make(x) if want_gx else None
     gz = make(z) if want_gz else None
     g_ls = make(lengthscale) if want_ls else None
@@ -1256,8 +1271,8 @@ def gp_periodic_bwd(x, z, lengthscale, period, variance, G, want=(True, True, Tr
     if empty or not (want_gx or want_gz or want_ls or want_period or want_var):
         return gx, gz, g_ls, g_period, g_var
     lib = _lib.load()
-    nbytes = lib.pa_gp_periodic_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _gp_workspace(lib.pa_gp_periodic_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz),
+                                                        int(forced_splits)), x)
     check(lib.pa_gp_periodic_bwd(_dtype(x), _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(), _ptr(period),
                                  period.numel(), _ptr(variance), _ptr(G), N, M, D, _ptr(gx), _ptr(gz), _ptr(g_ls),
                                  _ptr(g_period), _ptr(g_var), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
@@ -1270,19 +1285,16 @@ GP_DOT_FLUSH = 1024                       # (GPD_FLUSH: the longest sum of gp_do
 
 def _gp_dot_args(x, z, variance, bias, degree):
     _require_gpu(x, z, variance, bias)
-    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_dot: x [N, D], z [M, D]"
+    _gp_points("gp_dot", x, z)
     assert isinstance(degree, int), "gp_dot: degree is an int"
     D = x.shape[1]
     if not 1 <= D <= GP_KERNEL_MAX_D or not 1 <= degree <= GP_DOT_MAX_DEGREE:
         raise Unsupported("pyro_amd: gp_dot: D=%d outside [1, %d] or degree=%d outside [1, %d]"
                           % (D, GP_KERNEL_MAX_D, degree, GP_DOT_MAX_DEGREE))
-    for t in (z, variance, bias):
-        if t is not None and t.dtype != x.dtype:
-            raise ValueError("pyro_amd: gp_dot: one dtype throughout, got %s and %s" % (x.dtype, t.dtype))
+    _gp_one_dtype("gp_dot", x, (z, variance, bias))
     if any(t is not None and t.numel() != 1 for t in (variance, bias)):
         raise ValueError("pyro_amd: gp_dot: variance and bias have one element each")
-    return (x.contiguous(), None if z is None else z.contiguous(), None if variance is None else variance.contiguous(),
-            None if bias is None else bias.contiguous())
+    return _gp_contiguous(x, z, variance, bias)
 
 
 def gp_dot_fwd(x, z, variance, bias, degree):
@@ -1291,13 +1303,11 @@ def gp_dot_fwd(x, z, variance, bias, degree):
     kernel, or None for 1 and 0.  D over GP_KERNEL_MAX_D or a degree outside [1, GP_DOT_MAX_DEGREE] raises Unsupported; an
     empty result makes no launch."""
     x, z, variance, bias = _gp_dot_args(x, z, variance, bias, degree)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    K = x.new_empty((N, M))
+    N, M, K = _gp_new_K(x, z)
     if N == 0 or M == 0:
         return K
-    check(_lib.load().pa_gp_dot_fwd(_dtype(x), _ptr(x), _ptr(z), _ptr(variance), _ptr(bias), degree, _ptr(K), N, M, D,
-                                    _stream()))
+    check(_lib.load().pa_gp_dot_fwd(_dtype(x), _ptr(x), _ptr(z), _ptr(variance), _ptr(bias), degree, _ptr(K), N, M,
+                                    x.shape[1], _stream()))
     return K
 
 
@@ -1307,15 +1317,10 @@ def gp_dot_bwd(x, z, variance, bias, degree, G, want=(True, True, True, True), f
     is recomputed from the inputs -- it is not an argument -- in ONE pass over G, then a fixed-order float64 finalize
     (pa_gp_dot_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the number of column splits (tests)."""
     x, z, variance, bias = _gp_dot_args(x, z, variance, bias, degree)
-    _require_gpu(G)
-    N, D = x.shape
-    M = N if z is None else z.shape[0]
-    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_dot_bwd: G [N, M] of x's dtype"
-    G = G.contiguous()
+    N, M, G, empty, make = _gp_incoming("gp_dot_bwd", x, z, G)
+    D = x.shape[1]
     want_gx, want_gz, want_var, want_bias = (bool(w) for w in want)
     want_gz, want_var, want_bias = want_gz and z is not None, want_var and variance is not None, want_bias and bias is not None
-    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
-    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
     gx = make(x) if want_gx else None
     gz = make(z) if want_gz else None
     g_var = make(variance) if want_var else None
@@ -1323,8 +1328,7 @@ def gp_dot_bwd(x, z, variance, bias, degree, G, want=(True, True, True, True), f
     if empty or not (want_gx or want_gz or want_var or want_bias):
         return gx, gz, g_var, g_bias
     lib = _lib.load()
-    nbytes = lib.pa_gp_dot_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _gp_workspace(lib.pa_gp_dot_bwd_workspace(N, M, D, int(z is None), int(want_gx), int(want_gz), int(forced_splits)), x)
     check(lib.pa_gp_dot_bwd(_dtype(x), _ptr(x), _ptr(z), _ptr(variance), _ptr(bias), degree, _ptr(G), N, M, D, _ptr(gx),
                             _ptr(gz), _ptr(g_var), _ptr(g_bias), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
     return gx, gz, g_var, g_bias
@@ -1350,7 +1354,7 @@ def _gp_compose_args(x, z, spec, params):
     bias, terms = spec
     factors = [f for _, fs in terms for f in fs]
     _require_gpu(x, z)
-    assert x.dim() == 2 and (z is None or (z.dim() == 2 and z.shape[1] == x.shape[1])), "gp_compose: x [N, U], z [M, U]"
+    _gp_points("gp_compose", x, z, "U")
     U = x.shape[1]
     if not gp_compose_fits(spec, U):
         raise Unsupported("pyro_amd: gp_compose: %d terms, %d factors over U=%d columns are outside the caps"
@@ -1367,15 +1371,12 @@ def _gp_compose_args(x, z, spec, params):
         D = len(cols)
         n_aux = {1: (1,), 5: (1, D)}.get(kind, ())
         _require_gpu(variance, lengthscale, aux)
-        for p in (z, variance, lengthscale, aux):
-            if p is not None and p.dtype != x.dtype:
-                raise ValueError("pyro_amd: gp_compose: one dtype throughout, got %s and %s" % (x.dtype, p.dtype))
+        _gp_one_dtype("gp_compose", x, (z, variance, lengthscale, aux))
         if (variance.numel() != 1 or lengthscale.numel() not in (1, D) or (aux is None) != (not n_aux)
                 or (aux is not None and aux.numel() not in n_aux) or not all(0 <= c < U for c in cols)):
             raise ValueError("pyro_amd: gp_compose: factor %d: variance of 1 element, lengthscale of 1 or D, scale_mixture "
                              "of 1 / period of 1 or D where the kind takes one, columns inside [0, U)" % f)
-        variance, lengthscale = variance.contiguous(), lengthscale.contiguous()
-        aux = None if aux is None else aux.contiguous()
+        variance, lengthscale, aux = _gp_contiguous(variance, lengthscale, aux)
         keep.append((variance, lengthscale, aux))
         fa = d.factor[f]
         fa.variance, fa.lengthscale, fa.aux = _ptr(variance), _ptr(lengthscale), _ptr(aux)
@@ -1384,7 +1385,7 @@ def _gp_compose_args(x, z, spec, params):
             d.cols[col0 + k] = c
         col0 += D
     d.sum_d = col0
-    return d, x.contiguous(), None if z is None else z.contiguous(), keep
+    return (d,) + _gp_contiguous(x, z) + (keep,)
 
 
 def gp_compose_fwd(x, z, spec, params):
@@ -1395,8 +1396,7 @@ def gp_compose_fwd(x, z, spec, params):
     [1], the period [1 or D] or None; device tensors of x's dtype (f32 / f64), read by the kernel.  A spec outside the
     caps raises Unsupported; an empty result makes no launch."""
     d, x, z, keep = _gp_compose_args(x, z, spec, params)
-    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
-    K = x.new_empty((N, M))
+    N, M, K = _gp_new_K(x, z)
     if N == 0 or M == 0:
         return K
     check(_lib.load().pa_gp_compose_fwd(_dtype(x), ctypes.byref(d), _ptr(x), _ptr(z), _ptr(K), N, M, _stream()))
@@ -1410,15 +1410,10 @@ def gp_compose_bwd(x, z, spec, params, G, want=None, forced_splits=0):
     factor, then a fixed-order float64 finalize (pa_gp_compose_bwd): bit-reproducible.  ``forced_splits`` > 0 fixes the
     number of column splits (tests)."""
     d, x, z, keep = _gp_compose_args(x, z, spec, params)
-    _require_gpu(G)
-    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
-    assert tuple(G.shape) == (N, M) and G.dtype == x.dtype, "gp_compose_bwd: G [N, M] of x's dtype"
-    G = G.contiguous()
+    N, M, G, empty, make = _gp_incoming("gp_compose_bwd", x, z, G)
     if want is None:
         want = (True, True, [(True, True, True)] * len(keep))
     want_gx, want_gz = bool(want[0]), bool(want[1]) and z is not None
-    empty = N == 0 or M == 0                 # (no launch: the gradients of an empty matrix are zeros)
-    make = torch.zeros_like if empty else torch.empty_like       # (the finalize kernel writes every wanted entry)
     gx = make(x) if want_gx else None
     gz = make(z) if want_gz else None
     grads = [tuple(make(p) if w and p is not None else None for p, w in zip(ps, ws)) for ps, ws in zip(keep, want[2])]
@@ -1428,9 +1423,8 @@ def gp_compose_bwd(x, z, spec, params, G, want=None, forced_splits=0):
     for f, (gv, gl, ga) in enumerate(grads):
         out.g_variance[f], out.g_lengthscale[f], out.g_aux[f] = _ptr(gv), _ptr(gl), _ptr(ga)
     lib = _lib.load()
-    nbytes = lib.pa_gp_compose_bwd_workspace(ctypes.byref(d), N, M, int(z is None), int(want_gx), int(want_gz),
-                                             int(forced_splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _gp_workspace(lib.pa_gp_compose_bwd_workspace(ctypes.byref(d), N, M, int(z is None), int(want_gx), int(want_gz),
+                                                       int(forced_splits)), x)
     check(lib.pa_gp_compose_bwd(_dtype(x), ctypes.byref(d), _ptr(x), _ptr(z), _ptr(G), N, M, _ptr(gx), _ptr(gz),
                                 ctypes.byref(out), int(forced_splits), _ptr(ws), ws.numel() * 8, _stream()))
     return gx, gz, grads
@@ -1454,8 +1448,8 @@ def _gp_sgpr_args(x, xu, r, lengthscale, variance, alpha, family):
 
 
 def _gp_sgpr_workspace(lib, x, N, M, D, Q, backward, want_gx, want_gxu, forced_splits):
-    nbytes = lib.pa_gp_sgpr_workspace(_dtype(x), N, M, D, Q, int(backward), int(want_gx), int(want_gxu), int(forced_splits))
-    return torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    return _gp_workspace(lib.pa_gp_sgpr_workspace(_dtype(x), N, M, D, Q, int(backward), int(want_gx), int(want_gxu),
+                                                  int(forced_splits)), x)
 
 
 def gp_sgpr_fwd(x, xu, r, lengthscale, variance, alpha=None, family="rbf", forced_splits=0):
@@ -1572,8 +1566,7 @@ def gp_cond_bwd(x, xu, a, P, lengthscale, variance, alpha, g_loc, g_s, family="r
     if not empty and (gram or chain):
         lib = _lib.load()
         B2 = (2 * P.transpose(-1, -2).matmul(P)).contiguous() if chain else P      # (symmetric; only the chain reads it)
-        nbytes = lib.pa_gp_cond_workspace(_dtype(x), N, M, D, Q, int(want_gx), int(want_gxu), int(forced_splits))
-        ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+        ws = _gp_workspace(lib.pa_gp_cond_workspace(_dtype(x), N, M, D, Q, int(want_gx), int(want_gxu), int(forced_splits)), x)
         check(lib.pa_gp_cond_bwd(_dtype(x), family, _ptr(x), _ptr(xu), _ptr(a), _ptr(B2), _ptr(lengthscale),
                                  lengthscale.numel(), _ptr(variance), _ptr(alpha), _ptr(g_loc), _ptr(g_s), N, M, D, Q,
                                  _ptr(gx), _ptr(gxu), _ptr(g_ls), _ptr(g_var), _ptr(g_alpha), _ptr(ga), _ptr(Aw),

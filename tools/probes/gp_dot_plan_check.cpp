@@ -38,7 +38,7 @@ static void walk_lds(int D, size_t elem, bool backward) {
   // operand reads of s = x z^T: row 63, inner index kp - 1
   CHECK(((size_t)pa::GPK_TILE * stride + (size_t)(pa::GPK_TILE - 1) * stride + kp) * elem <= at, "operand read past the tiles");
   if (backward) {
-    for (size_t e = 0; e < (size_t)(pa::GPD_THREADS / 64) * pa::GPD_SUB * pa::GPD_WT * elem; ++e) lds[at++] += 1;
+    for (size_t e = 0; e < (size_t)pa::GPK_WAVES * pa::GPD_SUB * pa::GPD_WT * elem; ++e) lds[at++] += 1;
     const size_t off = pa::gpd_bwd_acc_offset(D, elem);
     CHECK(off % 8 == 0 && off >= at && off - at < 8, "accumulators at %zu after %zu", off, at);
     for (size_t e = 0; e < (size_t)pa::GPK_TILE * D * sizeof(double); ++e) lds[off + e] += 1;
@@ -54,7 +54,7 @@ static void check_call(int64_t N, int64_t M, int D, bool z_null, bool want_gx, b
   if (!pa::gpd_shape_ok(N, M, D, 1) || N == 0 || M == 0) return;
   const pa::GpdPlan pl = pa::gpd_plan(N, M, D, z_null, want_gx, want_gz, cus, forced);
   const pa::GpkLaunchPlan& g = pl.grid;
-  const pa::GpkLaunchPlan base = pa::gpk_launch_plan(N, M, D, want_gx, cus, forced);      // the split rule is the tree's
+  const pa::GpkLaunchPlan base = pa::gpk_launch_plan(N, M, D, pa::GPD_SCALARS, want_gx, cus, forced);      // the split rule is the tree's
   CHECK(g.splits == base.splits && g.workgroups == base.workgroups && g.tiles_per_split == base.tiles_per_split, "split rule");
   CHECK(g.splits >= 1 && g.workgroups == g.row_blocks * g.splits && g.workgroups <= pa::GPK_MAX_WORKGROUPS, "grid");
   CHECK(pl.rows_part == want_gx && pl.cols_part == (z_null ? want_gx : want_gz) && pl.sym == z_null, "parts");

@@ -85,7 +85,7 @@ static void check_call(int64_t N, int64_t M, int D, size_t elem, bool z_null, bo
                        int forced, bool walk) {
   if (z_null && N != M) return;
   if (!pa::gpk_shape_ok(0, N, M, D, 1) || N == 0 || M == 0) return;
-  const pa::GpkCallPlan cp = pa::gpk_call_plan(N, M, D, z_null, want_gx, want_gz, cus, forced);
+  const pa::GpkCallPlan cp = pa::gpk_call_plan(N, M, D, pa::gpk_record_doubles(D), z_null, want_gx, want_gz, cus, forced);
   CHECK(cp.run_x || cp.run_z, "nothing runs");
   CHECK(cp.run_z == (want_gz && !z_null), "run_z");
   CHECK(cp.bytes == cp.x.bytes + cp.z.bytes && cp.z_offset_doubles * sizeof(double) == cp.x.bytes, "offsets");
@@ -132,7 +132,7 @@ int main() {
   CHECK(!pa::gpk_shape_ok(0, pa::GPK_MAX_POINTS, 1, 3, 1), "size limit");
   check_call(1000000, 32, 8, 4, false, true, true, 256, 0, true);       // Xu [32, D] against X [1e6, D]
   {
-    const pa::GpkCallPlan cp = pa::gpk_call_plan(1000000, 32, 8, false, true, true, 256, 0);
+    const pa::GpkCallPlan cp = pa::gpk_call_plan(1000000, 32, 8, pa::gpk_record_doubles(8), false, true, true, 256, 0);
     CHECK(cp.z.row_blocks == 1 && cp.z.splits >= 256, "32 rows against 1e6 columns run on %d workgroups", cp.z.splits);
   }
   check_call(pa::GPK_MAX_POINTS - 1, 64, 64, 8, false, true, true, 256, 0, false);

@@ -37,7 +37,7 @@ static void walk_lds(int D, size_t elem, bool backward) {
   for (size_t e = 0; e < (size_t)2 * pa::GPK_TILE * stride * elem; ++e) lds[e] += 1;
   const size_t head = pa::gpk_lds_head_bytes(D, elem);
   CHECK(head % 8 == 0 && head >= (size_t)2 * pa::GPK_TILE * stride * elem, "head=%zu", head);
-  const size_t doubles = (size_t)2 * D + (backward ? (size_t)(pa::GPK_TILE + 2 * pa::GPP_WAVES) * D : 0);
+  const size_t doubles = (size_t)2 * D + (backward ? (size_t)(pa::GPK_TILE + 2 * pa::GPK_WAVES) * D : 0);
   for (size_t e = 0; e < doubles * sizeof(double); ++e) lds[head + e] += 1;
   CHECK(head + doubles * sizeof(double) == bytes, "LDS ends at %zu of %zu", head + doubles * sizeof(double), bytes);
   for (size_t e = 0; e < bytes; ++e)
@@ -86,12 +86,12 @@ static void walk_launch(const pa::GpkLaunchPlan& pl, double* ws, size_t ws_doubl
 static void check_call(int64_t N, int64_t M, int D, bool z_null, bool want_gx, bool want_gz, int cus, int forced, bool walk) {
   if (z_null && N != M) return;
   if (!pa::gpp_shape_ok(N, M, D, 1, D) || N == 0 || M == 0) return;
-  const pa::GpkCallPlan cp = pa::gpp_call_plan(N, M, D, z_null, want_gx, want_gz, cus, forced);
+  const pa::GpkCallPlan cp = pa::gpk_call_plan(N, M, D, pa::gpp_record_doubles(D), z_null, want_gx, want_gz, cus, forced);
   CHECK(cp.run_x || cp.run_z, "nothing runs");
   CHECK(cp.run_z == (want_gz && !z_null), "run_z");
   CHECK(cp.bytes == cp.x.bytes + cp.z.bytes && cp.z_offset_doubles * sizeof(double) == cp.x.bytes, "offsets");
   // the split rule is gp_kernel_plan.h's: same grid, larger scalar records
-  const pa::GpkCallPlan base = pa::gpk_call_plan(N, M, D, z_null, want_gx, want_gz, cus, forced);
+  const pa::GpkCallPlan base = pa::gpk_call_plan(N, M, D, pa::gpk_record_doubles(D), z_null, want_gx, want_gz, cus, forced);
   CHECK(cp.x.splits == base.x.splits && cp.z.splits == base.z.splits && cp.x.workgroups == base.x.workgroups, "split rule");
   if (!walk) return;
   std::vector<double> ws(cp.bytes / sizeof(double), 0.0);
