@@ -1243,6 +1243,34 @@ int pa_gp_compose_bwd(int dtype, const pa_gp_compose_spec* spec, const void* x, 
                       int64_t M, void* gx, void* gz, const pa_gp_compose_grads* grads, int forced_splits,
                       void* workspace, size_t workspace_bytes, pa_stream_t stream);
 
+/* ---- csrc/gp_wrap.hip: a stationary covariance under an output transform and a vertical scaling, ONE launch ----------
+ * Replaces Exponent, Warping (owarping_coef) and VerticalScaling of pyro/contrib/gp/kernels/kernel.py over a stationary
+ * child, which apply two to 2 n_coef element-wise passes to the child's [N, M] matrix and keep them for autograd, and
+ * Cosine of kernels/periodic.py:
+ *   K[i, j] = a_i * q(variance * f(r2_ij)) * b_j,   r2 and r as for pa_gp_kernel_* (direct differences, float64)
+ * family: one of pa_gp_kernel's five or PA_GP_COSINE, f = cos(r).  q: PA_GP_Q_IDENTITY, PA_GP_Q_EXP, or PA_GP_Q_POLY,
+ * q(k) = sum_c coef[c] k^c with 1 <= n_coef <= 8 HOST float64 coefficients that travel to the kernel by value (more:
+ * PA_ERR_UNSUPPORTED; coef is not read for the other two).  a [N], b [M]: DEVICE vectors of the call's dtype, or NULL for
+ * 1; with z = NULL a serves both roles and b must be NULL, with a z of its own they come together.  A family of
+ * pa_gp_kernel's with the identity and no scaling is that entry point's, PA_ERR_INVALID here.  Everything else -- the
+ * points, the parameters, D <= 64, the two-sided backward that recomputes from the inputs, the workspace check, the
+ * fixed-order float64 finalize, forced_splits -- is the contract of pa_gp_kernel_*.  pa_gp_wrap_bwd adds g_a [N] and
+ * g_b [M] (needs b), one more column of the row records: rows_x / rows_z of pa_gp_wrap_bwd_workspace say whether gx or
+ * g_a, gz or g_b, is asked for.  The coefficients have no gradient. */
+#define PA_GP_COSINE 6
+#define PA_GP_Q_IDENTITY 0
+#define PA_GP_Q_EXP 1
+#define PA_GP_Q_POLY 2
+int pa_gp_wrap_fwd(int dtype, int family, int q, const double* coef, int n_coef, const void* x, const void* z,
+                   const void* lengthscale, int n_ls, const void* variance, const void* alpha, const void* a, const void* b,
+                   void* K, int64_t N, int64_t M, int64_t D, pa_stream_t stream);
+size_t pa_gp_wrap_bwd_workspace(int64_t N, int64_t M, int64_t D, int z_null, int rows_x, int rows_z, int forced_splits);
+int pa_gp_wrap_bwd(int dtype, int family, int q, const double* coef, int n_coef, const void* x, const void* z,
+                   const void* lengthscale, int n_ls, const void* variance, const void* alpha, const void* a, const void* b,
+                   const void* G, int64_t N, int64_t M, int64_t D, void* gx, void* gz, void* g_lengthscale, void* g_variance,
+                   void* g_alpha, void* g_a, void* g_b, int forced_splits, void* workspace, size_t workspace_bytes,
+                   pa_stream_t stream);
+
 /* ---- csrc/gp_sgpr.hip: the statistics of a sparse GP regression (DTC / VFE), streamed: Kuf [M, N] is never formed --
  * With Kuf[i, n] = k(xu_i, x_n) of the families above (same r2: direct differences, float64 up to the exponential):
  *   pa_gp_sgpr_fwd:  A [M, M] = Kuf Kuf^T (both triangles written, exactly symmetric),  b [M, Q] = Kuf r

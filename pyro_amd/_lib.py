@@ -409,7 +409,13 @@ _SIGNATURES = {
     "pa_gp_compose_bwd_workspace": (c_size_t, [POINTER(GpComposeSpec), c_int64, c_int64, c_int, c_int, c_int, c_int]),
     "pa_gp_compose_bwd": (c_int, [c_int, POINTER(GpComposeSpec), c_void_p, c_void_p, c_void_p, c_int64, c_int64,   # .. spec x z G N M
                                   c_void_p, c_void_p, POINTER(GpComposeGrads), c_int, c_void_p, c_size_t, c_void_p]),
-    "pa_gp_sgpr_workspace": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_wrap_fwd": (c_int, [c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_int,   # .. family q coef n x z ls n_ls
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),  # var alpha a b K N M D stream
+    "pa_gp_wrap_bwd_workspace": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "pa_gp_wrap_bwd": (c_int, [c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]           # var alpha a b G N M D
+                       + [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_void_p]),                                    # grads, splits ws stream
+    "pa_gp_sgpr_workspace": (c_size_t,[c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
     "pa_gp_sgpr_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,  # .. x xu r ls n_ls var alpha
                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,                           # A b N M D Q
                                c_int, c_void_p, c_size_t, c_void_p]),                                            # splits ws stream

@@ -5,9 +5,10 @@ stationary kernels form their covariance matrix and its gradient with csrc/gp_ke
 ``Product`` tree of them can take ONE launch of csrc/gp_compose.hip (``kernels.FUSED_GP_COMPOSE``, opt-in);
 ``Polynomial`` and ``Coregionalize`` form ``x . z`` on matrix cores with csrc/gp_dot.hip (``kernels.FUSED_GP_DOT``);
 sparse regression and the sparse variational model stream their statistics over the data (csrc/gp_sgpr.hip,
-csrc/gp_cond.hip).
+csrc/gp_cond.hip).  ``Cosine``, and ``Exponent``, ``Warping`` and ``VerticalScaling`` over a stationary kernel, write
+their matrix in ONE launch of csrc/gp_wrap.hip (``kernels.FUSED_GP_WRAP``); ``Brownian`` is torch operators only.
 
-Not here: VariationalGP and GPLVM; the Cosine, Brownian, Exponent, VerticalScaling and Warping kernels."""
+Not here: VariationalGP and GPLVM."""
 from . import kernels, likelihoods, models, util
 from .parameterized import Parameterized
 

@@ -1,6 +1,7 @@
 """Covariance functions of Gaussian-process models (the classes and arguments of pyro/contrib/gp/kernels; the code
 is this package's): the stationary families ``RBF``, ``RationalQuadratic``, ``Exponential``, ``Matern32``,
-``Matern52`` over ``Isotropy``; ``Periodic``; ``Polynomial`` and ``Coregionalize``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``.
+``Matern52`` over ``Isotropy``; ``Periodic``; ``Polynomial`` and ``Coregionalize``; ``Constant``, ``WhiteNoise``, ``Linear``; ``Sum`` and ``Product``;
+``Cosine`` and ``Brownian``; ``Transforming`` with ``Exponent``, ``VerticalScaling`` and ``Warping``.
 
 A stationary family has two routes, chosen in ``Isotropy.forward``.
 
@@ -37,6 +38,16 @@ routes above goes into ONE launch of pa_gp_compose_fwd (csrc/gp_compose.hip: at 
 factors, a union of 64 columns), with one backward pass for all leaves; the other terms (``WhiteNoise``, ``Constant``,
 ``Linear``, what exceeds the caps) are evaluated as before and added.  Fewer than two such leaves, or ``diag=True``: as before.
 
+``Cosine``, and ``Exponent``, ``Warping`` (its ``owarping_coef``) and ``VerticalScaling`` over a stationary leaf or
+``Cosine``, stacked at most as ``VerticalScaling(q(leaf))``, are ONE launch of pa_gp_wrap_fwd (``FUSED_GP_WRAP``,
+csrc/gp_wrap.hip): ``a_i q(variance f(r2_ij)) b_j`` with the leaf's own arithmetic, ``q`` the identity, ``exp`` or a
+polynomial of at most 8 coefficients, ``a`` / ``b`` the values of ``vscaling_fn``, which torch operators form so that
+autograd carries the gradient of the scale into the function, as it carries that of the points into ``iwarping_fn``.
+The backward recomputes everything from the inputs; nothing of size [N, M] is kept.  The leaf must meet the conditions
+of its kernel route.  Any other nesting, another child, ``diag=True``, more coefficients, or float64 with a polynomial
+AND a scaling (that backward does not fit the registers) apply the reference's torch operators to what the child
+returns.  ``Brownian`` has no kernel route.
+
 GP training is eager: the modules close over their data, so an SVI step over them is not captured into a graph
 (``util.train``, or ``SVI(..., hip_graph=False)``), and ``torch.linalg.cholesky`` synchronises in any case.
 """
@@ -53,6 +64,7 @@ from .parameterized import Parameterized
 FUSED_GP_KERNEL = True            # device f32 / f64, D <= kernels.GP_KERNEL_MAX_D: pa_gp_kernel_fwd / pa_gp_kernel_bwd
 FUSED_GP_PERIODIC = True          # the same conditions for Periodic: pa_gp_periodic_fwd / pa_gp_periodic_bwd
 FUSED_GP_DOT = True               # the same conditions for Polynomial / Coregionalize: pa_gp_dot_fwd / pa_gp_dot_bwd
+FUSED_GP_WRAP = True              # Cosine, and Exponent / Warping / VerticalScaling over a stationary leaf: pa_gp_wrap_*
 FUSED_GP_COMPOSE = False          # opt-in: Sum / Product trees with two or more such leaves in ONE launch (pa_gp_compose_*)
 
 
@@ -320,6 +332,10 @@ class Isotropy(Kernel):
         """The contiguous sliced inputs and the parameters when the kernel route applies, else None."""
         if not FUSED_GP_KERNEL or self._family is None:
             return None
+        return self._fused_inputs(X, Z)
+
+    def _fused_inputs(self, X, Z):
+        """The same without the switch and the family: the conditions on the tensors alone."""
         variance, lengthscale, alpha = self.variance, self.lengthscale, self._shape_parameter()
         tensors = [X, variance, lengthscale] + ([] if Z is None else [Z]) + ([] if alpha is None else [alpha])
         if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == X.dtype for t in tensors):
@@ -659,3 +675,195 @@ class Linear(Kernel):
         if X.size(1) != Z.size(1):
             raise ValueError("Inputs must have the same number of features.")
         return self.variance * X.matmul(Z.t())
+
+
+# ---- Cosine, Brownian ------------------------------------------------------------------------------------------------
+@_dispatcher_op("gp_wrap")
+class _WrappedCovariance(torch.autograd.Function):
+    """K = a_i q(variance * f(r2_ij)) b_j in ONE launch (csrc/gp_wrap.hip); the gradient recomputes everything from the
+    saved INPUTS (the output may be modified in place by the caller), one pass over the incoming gradient per side.
+    ``q``: None, "exp" or a tuple of polynomial coefficients (constants: no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, z, lengthscale, variance, alpha, a, b, family, q):
+        from ... import kernels
+        ctx.family, ctx.q = family, q
+        ctx.save_for_backward(x, z, lengthscale, variance, alpha, a, b)
+        return kernels.gp_wrap_fwd(x, z, lengthscale.reshape(-1), variance.reshape(-1),
+                                   None if alpha is None else alpha.reshape(-1), family, q, a, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ... import kernels
+        x, z, lengthscale, variance, alpha, a, b = ctx.saved_tensors
+        gx, gz, gl, gv, gal, ga, gb = kernels.gp_wrap_bwd(
+            x, z, lengthscale.reshape(-1), variance.reshape(-1), None if alpha is None else alpha.reshape(-1), g,
+            ctx.family, ctx.q, a, b, list(ctx.needs_input_grad[:7]))
+        return (gx, gz, None if gl is None else gl.reshape(lengthscale.shape),
+                None if gv is None else gv.reshape(variance.shape),
+                None if gal is None else gal.reshape(alpha.shape), ga, gb, None, None)
+
+
+class Cosine(Isotropy):
+    """variance * cos(r).  Its kernel route is the wrapped covariance kernel's (``FUSED_GP_WRAP``) under the conditions
+    of the stationary families; ``_family`` stays None, so that the composite and the streamed sparse routes treat it
+    as a torch-route leaf."""
+
+    def forward(self, X, Z=None, diag=False):
+        if diag:
+            return self._diag(X)
+        fused = self._fused_inputs(X, Z) if FUSED_GP_WRAP else None
+        if fused is not None:
+            return _WrappedCovariance.invoke(*fused, None, None, "cosine", None)
+        return self._torch_forward(X, Z)
+
+    def _torch_forward(self, X, Z):
+        return self.variance * torch.cos(self._scaled_dist(X, Z))
+
+
+class Brownian(Kernel):
+    """Two-sided Brownian motion over ONE feature: variance * min(|x|, |z|) where x and z have the same sign, else 0.
+    No kernel route: it is one element-wise pass over [N, M] with nothing to fuse."""
+
+    def __init__(self, input_dim, variance=None, active_dims=None):
+        if input_dim != 1:
+            raise ValueError("Input dimensional for Brownian kernel must be 1.")
+        super().__init__(input_dim, active_dims)
+        variance = torch.tensor(1.0) if variance is None else variance
+        self.variance = PyroParam(variance, constraints.positive)
+
+    def forward(self, X, Z=None, diag=False):
+        X = self._slice_input(X)
+        if diag:
+            return self.variance * X.abs().squeeze(1)
+        Zt = (X if Z is None else self._slice_input(Z)).t()
+        if X.size(1) != Zt.size(0):
+            raise ValueError("Inputs must have the same number of features.")
+        return torch.where(X.sign() == Zt.sign(), self.variance * torch.min(X.abs(), Zt.abs()),
+                           X.new_zeros(X.size(0), Zt.size(1)))
+
+
+# ---- kernels derived from a kernel ---------------------------------------------------------------------------------------
+def _horner(K, coef):
+    value = coef[-1]
+    for c in reversed(coef[:-1]):
+        value = c + value * K
+    return value
+
+
+def _peel(kern):
+    """``kern`` as (vscaling_fn, iwarping_fn, q, leaf) when it is VerticalScaling(q(leaf)) with either layer optional,
+    q one of Exponent / Warping and the leaf a stationary kernel or Cosine -- what ONE wrapped launch evaluates -- else
+    None.  A bare stationary leaf is None as well: it has a route of its own."""
+    from ... import kernels as hip
+    scale = warp = q = None
+    if isinstance(kern, VerticalScaling):
+        scale, kern = kern.vscaling_fn, kern.kern
+    if isinstance(kern, Exponent):
+        q, kern = "exp", kern.kern
+    elif isinstance(kern, Warping):
+        warp, q, kern = kern.iwarping_fn, kern.owarping_coef and tuple(kern.owarping_coef), kern.kern
+    if not isinstance(kern, Isotropy):
+        return None
+    family = "cosine" if isinstance(kern, Cosine) else kern._family
+    if family is None:
+        return None
+    if isinstance(q, tuple) and len(q) > hip.GP_WRAP_MAX_COEF:
+        return None
+    if q is None and scale is None and kern._family is not None:
+        return None
+    return scale, warp, q, kern, family
+
+
+def _wrapped(kern, X, Z):
+    """K(X, Z) of a tree that ``_peel`` takes, else None.  ``vscaling_fn`` and ``iwarping_fn`` are evaluated ONCE, with
+    torch operators; where the leaf then meets the conditions of its kernel route the rest is one launch, otherwise the
+    reference's operators are applied to the same pieces."""
+    parts = _peel(kern)
+    if parts is None:
+        return None
+    scale, warp, q, leaf, family = parts
+    a = b = None
+    if scale is not None:
+        a, b = scale(X), None if Z is None else scale(Z)
+    if warp is not None:
+        X, Z = warp(X), None if Z is None else warp(Z)
+    fused = leaf._fused_inputs(X, Z) if isinstance(leaf, Cosine) else leaf._fused(X, Z)
+    if fused is not None:
+        sizes = (fused[0].size(0), None if fused[1] is None else fused[1].size(0))
+        scales_fit = all(t is None or (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == fused[0].dtype
+                                       and tuple(t.shape) == (n,)) for t, n in zip((a, b), sizes))
+        if scales_fit and not (isinstance(q, tuple) and a is not None and fused[0].dtype == torch.float64):
+            return _WrappedCovariance.invoke(*fused, a, b, family, q)
+    K = leaf(X, Z)
+    K = K if q is None else (K.exp() if q == "exp" else _horner(K, q))
+    return K if a is None else a.unsqueeze(1) * K * (a if b is None else b).unsqueeze(0)
+
+
+class Transforming(Kernel):
+    """Kernels derived from a kernel ``kern``; ``input_dim`` and ``active_dims`` are the child's."""
+
+    def __init__(self, kern):
+        if not isinstance(kern, Kernel):
+            raise TypeError("The original kernel of a transforming kernel must be a Kernel instance.")
+        super().__init__(kern.input_dim, kern.active_dims)
+        self.kern = kern
+
+    def forward(self, X, Z=None, diag=False):
+        if not diag and FUSED_GP_WRAP:
+            K = _wrapped(self, X, Z)
+            if K is not None:
+                return K
+        return self._plain(X, Z, diag)
+
+    def _child(self, X, Z, diag):
+        """What the child returns.  A nesting that ONE launch does not take stays in torch operators down to its leaf:
+        a child that is itself derived does not launch for its part of it."""
+        if isinstance(self.kern, Transforming):
+            return self.kern._plain(X, Z, diag)
+        return self.kern(X, Z, diag=diag)
+
+
+class Exponent(Transforming):
+    """exp(k(x, z))."""
+
+    def _plain(self, X, Z, diag):
+        return self._child(X, Z, diag).exp()
+
+
+class VerticalScaling(Transforming):
+    """f(x) k(x, z) f(z) for a function ``vscaling_fn`` of the inputs that returns one number per point."""
+
+    def __init__(self, kern, vscaling_fn):
+        super().__init__(kern)
+        self.vscaling_fn = vscaling_fn
+
+    def _plain(self, X, Z, diag):
+        a = self.vscaling_fn(X)
+        if diag:
+            return a * self._child(X, Z, diag) * a
+        b = a if Z is None else self.vscaling_fn(Z)
+        return a.unsqueeze(1) * self._child(X, Z, diag) * b.unsqueeze(0)
+
+
+class Warping(Transforming):
+    """q(k(f(x), f(z))): ``iwarping_fn`` f warps the inputs (deep kernel learning), ``owarping_coef`` are the
+    coefficients of the polynomial q, lowest first: a list of non-negative ints, constants without a gradient.  (A
+    negative coefficient is refused whatever its type; the reference lets a negative int pass.)"""
+
+    def __init__(self, kern, iwarping_fn=None, owarping_coef=None):
+        super().__init__(kern)
+        self.iwarping_fn = iwarping_fn
+        if owarping_coef is not None:
+            if any(coef < 0 for coef in owarping_coef):
+                raise ValueError("Coefficients of the polynomial must be a non-negative integer.")
+            if len(owarping_coef) < 2 and sum(owarping_coef) == 0:
+                raise ValueError("The ouput warping polynomial should have a degree of at least 1.")
+        self.owarping_coef = owarping_coef
+
+    def _plain(self, X, Z, diag):
+        if self.iwarping_fn is not None:
+            X, Z = self.iwarping_fn(X), None if Z is None else self.iwarping_fn(Z)
+        K = self._child(X, Z, diag)
+        return K if self.owarping_coef is None else _horner(K, self.owarping_coef)

@@ -1,5 +1,6 @@
-// gp_families.h -- the five stationary families as device evaluators, the ONE copy that every Gaussian-process kernel
-// evaluates (gp_kernel.hip, gp_compose.hip, gp_sgpr.hip, gp_cond.hip): f(r2) and f'(r2) = df / d(r2), the reference's
+// gp_families.h -- the five stationary families (and the cosine, which gp_wrap.hip alone dispatches) as device
+// evaluators, the ONE copy that every Gaussian-process kernel evaluates (gp_kernel.hip, gp_wrap.hip, gp_compose.hip,
+// gp_sgpr.hip, gp_cond.hip): f(r2) and f'(r2) = df / d(r2), the reference's
 // guard r = sqrt(r2 + 1e-12) inside, the exponential of a float64 argument (gp_exp_of, which gp_periodic.hip takes as
 // well) and the switch over the family.  The guard and the hi / lo exponential are numerics that the tests' bounds were
 // derived with: they live here and nowhere else.  Stands on common.h alone, no tile geometry.
@@ -81,6 +82,30 @@ struct GpMatern52 {
     const T e = gp_exp_of<T>(-sr);
     f = (T(1) + (T)sr + T(5.0 / 3.0) * (T)r2) * e;
     df = e * (T(-5.0 / 6.0) - T(5.0 * 2.2360679774997896964 / 6.0) * (T)(r2 / r));
+    da = T(0);
+  }
+};
+
+// sin(a) and cos(a) for an argument held in float64.  In float32 the argument is split as in gp_exp_of,
+// cos(hi + lo) = cos(hi) - lo sin(hi): rounding a = r to float32 alone would cost r 2^-24 ABSOLUTE in cos(r).
+template <typename T>
+__device__ __forceinline__ void gp_sincos_of(double a, T& s, T& c) {
+  if constexpr (sizeof(T) == 8) {
+    s = sin(a), c = cos(a);
+  } else {
+    const float hi = (float)a, lo = (float)(a - (double)hi);
+    const float sh = sinf(hi), ch = cosf(hi);
+    s = fmaf(lo, ch, sh), c = fmaf(-lo, sh, ch);
+  }
+}
+// cos(r), PA_GP_COSINE: dispatched by gp_wrap.hip alone (GP_FAMILY_DISPATCH below is the five families of the others)
+template <typename T>
+struct GpCosine {
+  __device__ __forceinline__ static void eval(double r2, T, T& f, T& df, T& da) {
+    const double r = sqrt(r2 + 1e-12);
+    T s;
+    gp_sincos_of<T>(r, s, f);
+    df = T(-0.5) * s / (T)r;
     da = T(0);
   }
 };

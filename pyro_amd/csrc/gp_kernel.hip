@@ -45,40 +45,6 @@
 
 namespace pa {
 
-template <typename T>
-__device__ __forceinline__ void gp_inverse_lengthscale(const T* __restrict__ ls, int n_ls, int D, double* inv_l) {
-  for (int k = threadIdx.x; k < D; k += GPK_THREADS) inv_l[k] = 1.0 / (double)ls[n_ls == 1 ? 0 : k];
-}
-
-// r2 of the thread's 4 x 4 entries, in float64 for both dtypes: the difference, its scaling by 1 / l and the sum over
-// the features.  f(r2) = exp(-r2 / 2) magnifies a relative error of r2 by r2 / 2: in float32 the two roundings of
-// d = (x - z) / l and a sequential sum of 64 squares are 3e-5 relative in f at r2 = 130, as much as or more than the
-// float32 restatement on the CPU carries.  The float32 inputs are exact in float64, so r2 is that of the inputs
-// as given, to float64 rounding, and stays in float64 up to the exponential (gp_exp_of).
-template <typename T>
-__device__ __forceinline__ void gp_r2_tile(const T* xs, const T* zs, const double* inv_l, int D, int stride, int ty,
-                                           int tx, double (&acc)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
-  for (int k = 0; k < D; ++k) {
-    const double il = inv_l[k];
-    double xv[4], zv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) xv[r] = (double)xs[(4 * ty + r) * stride + k];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) zv[c] = (double)zs[(4 * tx + c) * stride + k];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const double d = (xv[r] - zv[c]) * il;
-        acc[r][c] = fma(d, d, acc[r][c]);
-      }
-  }
-}
-
 // ---- forward ---------------------------------------------------------------------------------------------------------
 template <typename T, template <typename> class FAM>
 __global__ __launch_bounds__(GPK_THREADS) void gp_kernel_fwd_kernel(const T* __restrict__ x, const T* __restrict__ z,

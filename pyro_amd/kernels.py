@@ -1430,6 +1430,85 @@ def gp_compose_bwd(x, z, spec, params, G, want=None, forced_splits=0):
     return gx, gz, grads
 
 
+GP_WRAP_FAMILIES = dict(GP_FAMILIES, cosine=6)      # (PA_GP_COSINE: gp_wrap_* alone)
+GP_WRAP_MAX_COEF = 8                      # (csrc/gp_wrap_plan.h GPW_MAX_COEF)
+
+
+def _gp_wrap_args(x, z, lengthscale, variance, alpha, family, q, a, b):
+    """(family, q kind, coefficients as a C array or None, their number) + the tensors, contiguous."""
+    family = GP_WRAP_FAMILIES.get(family, family)
+    assert family in (0, 1, 2, 3, 4, 6), "gp_wrap: family is one of %s" % sorted(GP_WRAP_FAMILIES)
+    _require_gpu(x, z, lengthscale, variance, alpha, a, b)
+    _gp_points("gp_wrap", x, z)
+    D = x.shape[1]
+    if q is None or q == "exp":
+        kind, coef, n_coef = (0 if q is None else 1), None, 0
+    else:
+        kind, n_coef = 2, len(q)
+        if not 1 <= n_coef <= GP_WRAP_MAX_COEF:
+            raise Unsupported("pyro_amd: gp_wrap: %d coefficients outside [1, %d]" % (n_coef, GP_WRAP_MAX_COEF))
+        if a is not None and x.dtype == torch.float64:      # (the backward of this variant does not fit the registers)
+            raise Unsupported("pyro_amd: gp_wrap: f64 with a polynomial and a scaling is not built")
+        coef = (ctypes.c_double * n_coef)(*[float(c) for c in q])
+    if not 1 <= D <= GP_KERNEL_MAX_D:
+        raise Unsupported("pyro_amd: gp_wrap: D=%d outside [1, %d]" % (D, GP_KERNEL_MAX_D))
+    _gp_one_dtype("gp_wrap", x, (z, lengthscale, variance, alpha, a, b))
+    if lengthscale.numel() not in (1, D) or variance.numel() != 1 or (alpha is not None and alpha.numel() != 1):
+        raise ValueError("pyro_amd: gp_wrap: lengthscale has 1 or D elements, variance and scale_mixture 1")
+    if (family == 1) != (alpha is not None):
+        raise ValueError("pyro_amd: gp_wrap: scale_mixture goes with the RationalQuadratic family, and only with it")
+    N, M = x.shape[0], x.shape[0] if z is None else z.shape[0]
+    if (b is not None) != (a is not None and z is not None) or (a is not None and tuple(a.shape) != (N,)) \
+            or (b is not None and tuple(b.shape) != (M,)):
+        raise ValueError("pyro_amd: gp_wrap: a [N] and, with a z of its own, b [M], or neither")
+    if kind == 0 and a is None and family != 6:
+        raise ValueError("pyro_amd: gp_wrap: a stationary family without a transform or a scaling is gp_kernel_fwd's")
+    return (family, kind, coef, n_coef) + _gp_contiguous(x, z, lengthscale, variance, alpha, a, b)
+
+
+def gp_wrap_fwd(x, z, lengthscale, variance, alpha=None, family="rbf", q=None, a=None, b=None):
+    """K [N, M] = a_i q(variance * f(r2_ij)) b_j in ONE launch (pa_gp_wrap_fwd, csrc/gp_wrap.hip): f a family of
+    gp_kernel_fwd or "cosine" (GP_WRAP_FAMILIES), with its arguments and arithmetic; ``q`` None for the identity, "exp",
+    or a sequence of at most GP_WRAP_MAX_COEF polynomial coefficients (lowest first; host numbers, passed by value);
+    ``a`` [N] and ``b`` [M] device vectors of x's dtype or None for 1 (with z None, ``a`` alone serves both roles).  More
+    coefficients or D over GP_KERNEL_MAX_D raise Unsupported; an empty result makes no launch."""
+    family, kind, coef, n_coef, x, z, lengthscale, variance, alpha, a, b = _gp_wrap_args(
+        x, z, lengthscale, variance, alpha, family, q, a, b)
+    N, M, K = _gp_new_K(x, z)
+    if N == 0 or M == 0:
+        return K
+    check(_lib.load().pa_gp_wrap_fwd(_dtype(x), family, kind, coef, n_coef, _ptr(x), _ptr(z), _ptr(lengthscale),
+                                     lengthscale.numel(), _ptr(variance), _ptr(alpha), _ptr(a), _ptr(b), _ptr(K), N, M,
+                                     x.shape[1], _stream()))
+    return K
+
+
+def gp_wrap_bwd(x, z, lengthscale, variance, alpha, G, family="rbf", q=None, a=None, b=None, want=(True,) * 7,
+                forced_splits=0):
+    """The gradients of gp_wrap_fwd's K given G = dL/dK [N, M]: (gx, gz, g_lengthscale, g_variance, g_alpha, g_a, g_b),
+    ``None`` where ``want`` is false or the argument is absent (gz and g_b also when z is None: gx and g_a then take both
+    roles).  Everything is recomputed from the inputs in one pass over G per side that wants a gradient, then a
+    fixed-order float64 finalize (pa_gp_wrap_bwd): bit-reproducible.  The coefficients of ``q`` have no gradient.
+    ``forced_splits`` > 0 fixes the number of column splits (tests)."""
+    family, kind, coef, n_coef, x, z, lengthscale, variance, alpha, a, b = _gp_wrap_args(
+        x, z, lengthscale, variance, alpha, family, q, a, b)
+    N, M, G, empty, make = _gp_incoming("gp_wrap_bwd", x, z, G)
+    D = x.shape[1]
+    present = (x, z, lengthscale, variance, alpha, a, b)
+    grads = [make(t) if w and t is not None else None for w, t in zip(want, present)]
+    if empty or all(g is None for g in grads):
+        return tuple(grads)
+    gx, gz, g_ls, g_var, g_alpha, g_a, g_b = grads
+    rows_x, rows_z = int(gx is not None or g_a is not None), int(gz is not None or g_b is not None)
+    lib = _lib.load()
+    ws = _gp_workspace(lib.pa_gp_wrap_bwd_workspace(N, M, D, int(z is None), rows_x, rows_z, int(forced_splits)), x)
+    check(lib.pa_gp_wrap_bwd(_dtype(x), family, kind, coef, n_coef, _ptr(x), _ptr(z), _ptr(lengthscale), lengthscale.numel(),
+                             _ptr(variance), _ptr(alpha), _ptr(a), _ptr(b), _ptr(G), N, M, D, _ptr(gx), _ptr(gz), _ptr(g_ls),
+                             _ptr(g_var), _ptr(g_alpha), _ptr(g_a), _ptr(g_b), int(forced_splits), _ptr(ws), ws.numel() * 8,
+                             _stream()))
+    return tuple(grads)
+
+
 GP_SGPR_MAX_M = {torch.float32: 512, torch.float64: 256}      # (csrc/gp_sgpr_plan.h gps_max_m)
 GP_SGPR_MAX_Q = 16
 
